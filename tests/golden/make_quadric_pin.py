@@ -1,11 +1,11 @@
 """Generate tests/golden/sdl_quadrics_pin.json from the reference's one integrator output.
 
-/root/reference/examples/sdl_quadrics.jpg (README.md:7) is raysnail's own 800x500 render of
+examples/sdl_quadrics.jpg (the reference's README.md:7) is raysnail's own 800x500 render of
 sdl/quadric.sdl through the CLI (src/bin/raysnail.rs:311-445: CLI camera / light conventions, depth 8,
 clamp * 255.5 -> u8, then saved by the author as a JPEG). This script decodes it with PIL and stores
 only derived numbers -- the global mean RGB and 25x25-pixel block means (32 x 20 blocks) plus each
-block's pixel standard deviation -- so the GPU test on the box (where /root/reference does not
-exist) can compare a fresh render of the same scene against the reference's render.
+block's pixel standard deviation -- so the tests compare a fresh render of the same scene against the
+reference's render block by block.
 
 usage: python tests/golden/make_quadric_pin.py [path/to/sdl_quadrics.jpg]
 """
@@ -17,7 +17,7 @@ import numpy as np
 
 BLOCK = 25
 HERE = os.path.dirname(os.path.abspath(__file__))
-DEFAULT = "/root/reference/examples/sdl_quadrics.jpg"
+DEFAULT = os.path.join(HERE, "reference", "sdl_quadrics.jpg")   # a copy of the reference's examples/sdl_quadrics.jpg
 
 
 def block_stats(rgb01: np.ndarray, block: int = BLOCK):

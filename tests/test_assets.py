@@ -6,7 +6,7 @@ ConstantMedium's draw checked against the oracle's probes.
 Pinning: no reference fixture covers these paths (the reference has one test, transform.rs:187-206;
 its Perlin tables come from an OS-seeded FastRng, noise.rs:44-66 via scene.rs:424). The checks here
 pin the oracle to restatements written independently in Python from the reference source; the
-earth-map test decodes the reference's own examples/earth-map.png where the tree exists.
+earth-map test decodes the first rows of the reference's own examples/earth-map.png (tests/golden/reference/).
 """
 import ctypes as C
 import math
@@ -21,7 +21,7 @@ from raysnail_amd import _abi as A
 from raysnail_amd import api, host_lib, scenes
 from raysnail_amd.scenes import fma as _fma
 
-EARTH = "/root/reference/examples/earth-map.png"
+EARTH = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "reference", "earth-map_rows64.png")
 
 
 # ------------------------------------------------------------------------------------- PNG ----
@@ -114,9 +114,9 @@ def test_png_reader_rejects_oversized_headers(tmp_path, w, h):
         host_lib.png_load(str(p))
 
 
-@pytest.mark.skipif(not os.path.exists(EARTH), reason="reference tree absent")
 def test_png_reader_on_reference_earth_map():
-    """examples/earth-map.png (1920x960 RGB): the C++ reader against zlib + numpy unfiltering."""
+    """The first 64 rows of examples/earth-map.png (1920 wide, RGB) with the file's own filter bytes
+    (tests/golden/make_earth_rows.py): the C++ reader against zlib + numpy unfiltering."""
     data = open(EARTH, "rb").read()
     pos, idat, hdr = 8, b"", None
     while pos < len(data):
@@ -128,7 +128,7 @@ def test_png_reader_on_reference_earth_map():
             idat += data[pos + 8:pos + 8 + n]
         pos += 12 + n
     w, h, depth, ctype = hdr[:4]
-    assert (depth, ctype) == (8, 2)
+    assert (w, h, depth, ctype) == (1920, 64, 8, 2)
     raw = np.frombuffer(zlib.decompress(idat), np.uint8).reshape(h, 1 + 3 * w)
     img = np.zeros((h, 3 * w), np.int32)
     for y in range(h):
@@ -502,7 +502,8 @@ def test_medium_uniform_hash(hip_lib):
 def test_new_scenes_realise_on_oracle(oracle_lib):
     """cornell_smoke / all_feature_scene / materials_scene build and render finite frames on the oracle."""
     from oracle.binding import OracleScene
-    for cam, world in (scenes.cornell_smoke(24, 24), scenes.all_feature_scene(24, 24), scenes.materials_scene(32, 20)):
+    for cam, world in (scenes.cornell_smoke(24, 24), scenes.all_feature_scene(24, 24, earth=scenes.synthetic_image()),
+                       scenes.materials_scene(32, 20)):
         photo = cam.take_photo().samples(4).depth(8).seed(1)
         img, st = OracleScene(world).render(cam.desc, photo.settings(), threads=4)
         assert np.isfinite(img).all() and st.segments > 0

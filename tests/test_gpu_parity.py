@@ -65,7 +65,7 @@ SCENES = {
     # §8(f)3: BlinnPhong, Perlin (all types / smoothings), Image (u, v), Isotropic media, Difference
     "materials": lambda: scenes.materials_scene(96, 64),
     "cornell_smoke": lambda: scenes.cornell_smoke(48, 48),
-    "all_feature": lambda: scenes.all_feature_scene(48, 48),
+    "all_feature": lambda: scenes.all_feature_scene(48, 48, earth=scenes.synthetic_image()),
     "box_field": lambda: _box_field(64, 48),
 }
 

@@ -1,11 +1,11 @@
 """The one reference-produced output of raysnail's integrator pins the whole path.
 
-/root/reference/examples/sdl_quadrics.jpg (README.md:7) is raysnail's own 800x500 render of
+examples/sdl_quadrics.jpg (the reference's README.md:7) is raysnail's own 800x500 render of
 sdl/quadric.sdl through the CLI: CLI camera (aperture 0.01, focus 10) and light conventions (the SDL
 light as a radius-12 sphere x1.7, no Cornell emitter), gradient sky, samples 122 -> 121, depth 8,
 one pass, clamp * 255.5 -> u8 (src/bin/raysnail.rs:311-445, 504-509), then stored as a JPEG.
 tests/golden/sdl_quadrics_pin.json holds its decoded global mean and 25x25-pixel block means
-(tests/golden/make_quadric_pin.py; the JPEG itself does not travel to the GPU box).
+(tests/golden/make_quadric_pin.py); tests/golden/reference/sdl_quadrics.jpg is a copy of the JPEG itself.
 
 Statistic: a z-score per block and channel (tests/pinlib.py: Monte Carlo standard error of both
 renders estimated from our render's pixel noise, plus 0.002 for JPEG quantisation); every one of the
@@ -31,7 +31,7 @@ import pytest
 import pinlib
 from raysnail_amd import scenes
 
-JPEG = "/root/reference/examples/sdl_quadrics.jpg"
+JPEG = os.path.join(pinlib.GOLDEN, "reference", "sdl_quadrics.jpg")   # a copy of the reference's examples/sdl_quadrics.jpg
 Z_MAX = 4.5
 GLOBAL_TOL = 0.003
 DELTA_MOVES = 0.002   # a block the coplanar effect moves (fixture blocks with |delta| above this)
@@ -54,7 +54,6 @@ def _failing(z):
     return np.abs(z).max(axis=-1) >= Z_MAX
 
 
-@pytest.mark.skipif(not os.path.exists(JPEG), reason="the reference checkout is not on this machine")
 def test_pin_file_is_the_reference_jpeg():
     from PIL import Image
     from importlib.util import module_from_spec, spec_from_file_location

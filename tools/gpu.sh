@@ -3,7 +3,7 @@
 # profiles/). Every GPU step has its own time limit and the session stops at the first failure.
 # usage: bash tools/gpu.sh <tag> <step> [<step> ...]
 #   tests    pytest -m gpu (every GPU test)
-#   bench    python bench.py (the driver's line: CPU baseline, row share)
+#   bench    python bench.py --full (the whole line: latency, roofline, CPU baseline, row share)
 #   trace    rocprofv3 kernel traces: bench frames (tools/render_once.py) and N=8 row-share frames
 #            (tools/share_frames.py) -> kernel_stats / kernel_trace csv
 #   pmc      FETCH_SIZE / WRITE_SIZE passes over bench frames + profiles/pmc_summary.json (tools/collect_pmc.py)
@@ -25,20 +25,23 @@ OUT=$R/gpurun_out/$TAG
 mkdir -p $OUT
 export TMPDIR=/tmp
 step() { local t=$1; shift; echo "== $* (limit ${t}s)" >> $OUT/steps.log; timeout -k 10 $t "$@"; local rc=$?; echo "   rc=$rc" >> $OUT/steps.log; return $rc; }
+# the A/B steps read the roofline and row-share fields, which bench.py reports under --full; a baseline worktree
+# from before that option reports them in every run
+full_of() { grep -q -- '"--full"' $1/bench.py && echo --full; }
 for s in "$@"; do
   case $s in
   tests)
     (cd $R && step 900 python -u -m pytest tests -x -v --timeout 300 --timeout-method thread -m gpu > $OUT/pytest_gpu.log 2>&1) || { echo "gpu tests failed"; tail -30 $OUT/pytest_gpu.log; exit 1; }
     tail -1 $OUT/pytest_gpu.log ;;
   bench)
-    (cd $R && step 300 python bench.py > $OUT/bench.json 2> $OUT/bench.err) || { echo "bench failed"; tail -20 $OUT/bench.err; exit 1; }
+    (cd $R && step 300 python bench.py --full > $OUT/bench.json 2> $OUT/bench.err) || { echo "bench failed"; tail -20 $OUT/bench.err; exit 1; }
     tail -1 $OUT/bench.json ;;
   trace)
     (cd /tmp && step 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -o trace -- python3 $R/tools/render_once.py 0 5 > $OUT/trace_frames.log 2>&1) || { echo "trace failed"; exit 1; }
     (cd /tmp && step 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/share -o share -- python3 $R/tools/share_frames.py 8 10 > $OUT/share_frames.log 2>&1) || { echo "share trace failed"; exit 1; } ;;
   pmc)
-    (cd /tmp && step 300 rocprofv3 --pmc FETCH_SIZE --output-format csv -d $OUT/pmc_fetch -o pmc -- python3 $R/bench.py --steps 3 --warmup 1 --cpu-baseline 0 --row-share 0 > /dev/null 2> $OUT/pmc_fetch.err) || { echo "pmc fetch failed"; exit 1; }
-    (cd /tmp && step 300 rocprofv3 --pmc WRITE_SIZE --output-format csv -d $OUT/pmc_write -o pmc -- python3 $R/bench.py --steps 3 --warmup 1 --cpu-baseline 0 --row-share 0 > /dev/null 2> $OUT/pmc_write.err) || { echo "pmc write failed"; exit 1; }
+    (cd /tmp && step 300 rocprofv3 --pmc FETCH_SIZE --output-format csv -d $OUT/pmc_fetch -o pmc -- python3 $R/bench.py --full --steps 3 --warmup 1 --cpu-baseline 0 --row-share 0 > /dev/null 2> $OUT/pmc_fetch.err) || { echo "pmc fetch failed"; exit 1; }
+    (cd /tmp && step 300 rocprofv3 --pmc WRITE_SIZE --output-format csv -d $OUT/pmc_write -o pmc -- python3 $R/bench.py --full --steps 3 --warmup 1 --cpu-baseline 0 --row-share 0 > /dev/null 2> $OUT/pmc_write.err) || { echo "pmc write failed"; exit 1; }
     FC=$(find $OUT/pmc_fetch -name '*counter_collection.csv' | head -1); WC=$(find $OUT/pmc_write -name '*counter_collection.csv' | head -1)
     (cd $R && python3 tools/collect_pmc.py "$FC" "$WC" $R/profiles/pmc_summary.json $TAG > /dev/null && cp $R/profiles/pmc_summary.json $OUT/pmc_summary_wavefront.json) || { echo "pmc summary failed"; exit 1; } ;;
   calib)
@@ -69,17 +72,17 @@ for s in "$@"; do
   ab)
     # this tree's bench line against the baseline worktree base/ (tools/ab_base.sh), 3 rounds interleaved
     for rep in 1 2 3; do
-      (cd $R/base && step 240 python3 bench.py --cpu-baseline 0 --steps 20 --warmup 5 > $OUT/ab_base_$rep.json 2> $OUT/ab_base.err) || { echo "base bench failed"; tail -5 $OUT/ab_base.err; exit 1; }
-      (cd $R && step 240 python3 bench.py --cpu-baseline 0 --steps 20 --warmup 5 > $OUT/ab_new_$rep.json 2> $OUT/ab_new.err) || { echo "bench failed"; tail -5 $OUT/ab_new.err; exit 1; }
+      (cd $R/base && step 240 python3 bench.py $(full_of $R/base) --cpu-baseline 0 --steps 20 --warmup 5 > $OUT/ab_base_$rep.json 2> $OUT/ab_base.err) || { echo "base bench failed"; tail -5 $OUT/ab_base.err; exit 1; }
+      (cd $R && step 240 python3 bench.py --full --cpu-baseline 0 --steps 20 --warmup 5 > $OUT/ab_new_$rep.json 2> $OUT/ab_new.err) || { echo "bench failed"; tail -5 $OUT/ab_new.err; exit 1; }
     done
     (cd $R && python3 tools/ab_report.py $OUT/ab_base_*.json -- $OUT/ab_new_*.json | tee $OUT/ab.txt) ;;
   variants)
     # bench.py of base/, this tree's product and every dev variant (raysnail_amd/lib/var_*.so, tools/build_variant.sh),
     # 2 rounds interleaved; frames of the variants are not checked here (dev bounds may be wrong on purpose)
-    B="--cpu-baseline 0 --steps 20 --warmup 5"
+    B="--full --cpu-baseline 0 --steps 20 --warmup 5"
     for rep in 1 2; do
       if [ -d $R/base ]; then
-        (cd $R/base && step 240 python3 bench.py $B > $OUT/v_base_$rep.json 2> $OUT/v.err) || { echo "base bench failed"; tail -5 $OUT/v.err; exit 1; }
+        (cd $R/base && step 240 python3 bench.py $(full_of $R/base) ${B#--full } > $OUT/v_base_$rep.json 2> $OUT/v.err) || { echo "base bench failed"; tail -5 $OUT/v.err; exit 1; }
       fi
       (cd $R && step 240 python3 bench.py $B > $OUT/v_prod_$rep.json 2> $OUT/v.err) || { echo "bench failed"; tail -5 $OUT/v.err; exit 1; }
       for v in $R/raysnail_amd/lib/var_*.so; do
@@ -166,7 +169,7 @@ for s in "$@"; do
   benchprof)
     # bench.py itself under rocprofv3 --kernel-trace --stats (the contract's "same command"): its bench line and the
     # kernel statistics, whose k_wfs_extend average the line's event-timed avg_launch_ms should agree with
-    (cd /tmp && step 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/benchprof -o bp -- python3 $R/bench.py --cpu-baseline 0 --row-share 0 > $OUT/bench_under_rocprof.json 2> $OUT/benchprof.err) || { echo "bench under rocprof failed"; tail -5 $OUT/benchprof.err; exit 1; }
+    (cd /tmp && step 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/benchprof -o bp -- python3 $R/bench.py --full --cpu-baseline 0 --row-share 0 > $OUT/bench_under_rocprof.json 2> $OUT/benchprof.err) || { echo "bench under rocprof failed"; tail -5 $OUT/benchprof.err; exit 1; }
     tail -1 $OUT/bench_under_rocprof.json
     # the line's roofline recomputed from the trace's statistics-frame launches (tools/trace_roofline.py)
     (cd $R && python3 tools/trace_roofline.py $OUT/benchprof/bp_kernel_trace.csv $OUT/bench_under_rocprof.json | tee $OUT/trace_roofline.json) ;;
@@ -217,7 +220,7 @@ for s in "$@"; do
     cat $OUT/passtrace.txt ;;
   abenv)
     # this build's bench line against the dev library with ABENV (a dev knob that turns a feature off), 3 rounds
-    B="--cpu-baseline 0 --steps 20 --warmup 5"
+    B="--full --cpu-baseline 0 --steps 20 --warmup 5"
     for rep in 1 2 3; do
       (cd $R && step 240 env RS_HIP_LIB=$R/raysnail_amd/lib/libraysnail_hip_dev.so $ABENV python3 bench.py $B > $OUT/abenv_off_$rep.json 2> $OUT/abenv.err) || { echo "dev bench failed"; tail -5 $OUT/abenv.err; exit 1; }
       (cd $R && step 240 python3 bench.py $B > $OUT/abenv_on_$rep.json 2> $OUT/abenv.err) || { echo "bench failed"; tail -5 $OUT/abenv.err; exit 1; }

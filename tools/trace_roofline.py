@@ -1,8 +1,8 @@
-"""Recompute bench.py's roofline field from a rocprofv3 kernel trace of the same bench.py run.
+"""Recompute bench.py's roofline field from a rocprofv3 kernel trace of the same bench.py --full run.
 
 usage: python tools/trace_roofline.py <kernel_trace.csv> <bench line .json>
 
-bench.py runs, in this order: `warmup` frames, `steps` timed (pipelined) frames, min(steps, 5) latency frames,
+bench.py --full runs, in this order: `warmup` frames, `steps` timed (pipelined) frames, min(steps, 5) latency frames,
 then `steps` statistics frames on one lane, each frame alone -- the frames its `avg_launch_ms` is event-timed on.
 Every frame of the workload enqueues the same launches, so the statistics frames' extend launches are the
 `launches_per_step` x `steps` dominant-kernel dispatches that follow the first (warmup + steps + latency) frames'
