@@ -182,8 +182,9 @@ struct Slot {
     size_t counts_clean = 0;  // leading entries of d_counts known to be zero (reset by the last frame's accumulate)
     hipStream_t acc_stream = nullptr;         // streaming wavefront: the batches' accumulates
     std::vector<hipEvent_t> bev;              // per batch: its paths done, its accumulate done
-    // the carried-path counts of the slot's last streaming frame (per lane and iteration), copied into pinned host
-    // memory at its end: they size the carried-extend grids of later frames of the same shape (Replica::hist)
+    // the carried-path and queued-path counts of the slot's last streaming frame (two words per lane and iteration),
+    // copied into pinned host memory at its end: they size the carried-extend and shading grids of later frames of
+    // the same shape (Replica::hist)
     uint32_t* h_hist = nullptr; size_t hist_cap = 0, hist_words = 0; uint64_t hist_sig = 0;
     hipEvent_t hist_ev = nullptr; bool hist_pending = false;
 
@@ -229,7 +230,7 @@ struct Replica {
     int32_t* d_ovf = nullptr; size_t ovf_cap = 0;   // traversal-stack overflow (entries beyond the LDS part)
     DScene* d_ds = nullptr;                 // ds in device memory (what the kernels read)
     DScene uploaded{};                      // the copy last written to d_ds
-    std::vector<uint32_t> hist;             // the latest completed streaming frame's carried counts (Slot::h_hist)
+    std::vector<uint32_t> hist;             // the latest completed streaming frame's carried and queued counts (Slot::h_hist)
     uint64_t hist_sig = 0;                  // and its schedule's signature
     std::vector<hipStream_t> pad_streams;   // dev A/B only (RS_PAD_STREAMS)
 
@@ -1858,7 +1859,7 @@ void render_enqueue(const rs_scene* s, Replica& R, const rs_camera_desc* cam, co
             const LaneSched& ln = f.lane[l];
             sig = splitmix64_h(sig ^ ln.Q ^ (ln.T << 40) ^ (ln.total << 1) ^ (uint64_t)ln.finish);
             hoff[l] = hwords;
-            hwords += ln.T;
+            hwords += 2 * ln.T;  // per iteration: the paths carried in, the paths queued for shading
         }
         for (Slot& o : R.slots) {
             if (!o.hist_pending) continue;
@@ -1956,7 +1957,7 @@ void render_enqueue(const rs_scene* s, Replica& R, const rs_camera_desc* cam, co
                  }
                  auto extend = [&](int part, uint64_t n_max) {
                      if (hint && part == kExtCarried) {
-                         const uint64_t est = R.hist[hoff[l] + t];
+                         const uint64_t est = R.hist[hoff[l] + 2 * t];
                          n_max = std::min<uint64_t>(n_max, est + est / 4 + 64ull * kBlock);
                      }
                      const uint32_t b = (uint32_t)std::min<uint64_t>(ext_cap, (n_max + kBlock - 1) / kBlock);
@@ -1983,8 +1984,13 @@ void render_enqueue(const rs_scene* s, Replica& R, const rs_camera_desc* cam, co
                  if (D > 0) {
                      uint64_t n_sh = window[l] + n_new;  // the paths it may shade: at most the live ones
 #ifndef RS_NO_SHADE_HINT  // (dev A/B)
-                     if (hint) {
-                         const uint64_t est = R.hist[hoff[l] + t];
+                     if (hint && cam_fused(sm, kExtCamera)) {
+                         // the camera launch shades most of its hits itself: the grid from the earlier frame's
+                         // queued count of the iteration (k_wfs_shade_all writes it next to the carried count)
+                         const uint64_t est = R.hist[hoff[l] + 2 * t + 1];
+                         n_sh = std::min<uint64_t>(n_sh, est + est / 4 + 64ull * kBlock);
+                     } else if (hint) {
+                         const uint64_t est = R.hist[hoff[l] + 2 * t];
                          n_sh = std::min<uint64_t>(n_sh, est + est / 4 + 64ull * kBlock + n_new);
                      }
 #endif
@@ -2023,11 +2029,11 @@ void render_enqueue(const rs_scene* s, Replica& R, const rs_camera_desc* cam, co
                      }
                      HIP_OK(hipEventRecord(L.fork_ev, L0));
                      HIP_OK(hipStreamWaitEvent(S, L.fork_ev, 0));
-                     // the frame's carried counts (counter slot 0 of each lane's iterations) for later frames' grids,
-                     // before the accumulate zeroes them
+                     // the frame's carried and queued counts (words 0 and 1 of each lane's iterations' counter blocks)
+                     // for later frames' grids, before the accumulate zeroes them
                      for (uint32_t l = 0; l < f.lanes; ++l)
-                         HIP_OK(hipMemcpy2DAsync(L.h_hist + hoff[l], sizeof(uint32_t), L.d_counts + f.lane[l].cnt_off,
-                                                 kWfsStride * sizeof(uint32_t), sizeof(uint32_t), f.lane[l].T,
+                         HIP_OK(hipMemcpy2DAsync(L.h_hist + hoff[l], 2 * sizeof(uint32_t), L.d_counts + f.lane[l].cnt_off,
+                                                 kWfsStride * sizeof(uint32_t), 2 * sizeof(uint32_t), f.lane[l].T,
                                                  hipMemcpyDeviceToHost, S));
                      HIP_OK(hipEventRecord(L.hist_ev, S));
                      L.hist_pending = true;
@@ -2227,15 +2233,19 @@ void render_finish(const rs_scene* s, Pending& P, rs_render_stats* stats) {
         kbytes = 80ull * seg;
     } else {
         // the streaming extend's library byte model, per iteration: ray records in (64 B)
-        // per carried path; the queue entry with the hit (16 B) per shaded segment; the record out (96 B + item
-        // + level) per live camera sample (written after its traversal for the ones that go on to shading:
-        // an upper bound); radiance out (24 B) per path ending in extend, + its throughput record and item
-        // in (36 B); radiance out for masked samples
+        // per carried path; the queue entry with the hit (16 B) per queued segment; the record out (96 B + item
+        // + level) per live camera sample (written after its traversal for the ones that go on to the shading
+        // launch, or after its in-place shading for a lean-class hit of the spheres mode's camera launch, whose
+        // survivors write the level-1 record and the others 24 B of radiance: an upper bound); radiance out (24 B)
+        // per path ending in extend unshaded, + its throughput record and item in (36 B); radiance out for masked
+        // samples. `fused`: the camera hits shaded inside the extend (word 1 of the statistics lines): they are
+        // neither queued nor ended there
         for (size_t l = 0; l < P.lanes.size(); ++l)
             for (uint64_t t = 0; t < P.lanes[l].T; ++t) {
                 const uint32_t* q = &P.qc[P.lanes[l].cnt_off + t * kWfsStride];
-                uint64_t live_new = 0, shaded = 0;
+                uint64_t live_new = 0, shaded = 0, fused = 0;
                 for (uint32_t k = 0; k < kStatLines; ++k) live_new += q[cix(kCntStat0 + (int)k)];
+                for (uint32_t k = 0; k < kStatLines; ++k) fused += q[cix(kCntStat0 + (int)k) + 1];
                 for (int k = 0; k < kWfsClasses; ++k) shaded += q[cix(1 + k)];
                 const uint64_t old = q[cix(0)], live = old + live_new;
                 if (P.lanes[l].finish && t + 1 == P.lanes[l].T) {
@@ -2246,17 +2256,17 @@ void render_finish(const rs_scene* s, Pending& P, rs_render_stats* stats) {
                     continue;
                 }
                 const uint64_t dead_new = P.inj[l][t] - live_new;
-                const uint64_t ended = live - shaded;
+                const uint64_t ended = live - shaded - fused;
                 seg += live;
                 kbytes += 64ull * old + 16ull * shaded + (uint64_t)P.rec_bytes * live_new + 60ull * ended + 24ull * dead_new;
 #ifdef RS_DEV_KNOBS
                 if (s->dump_iters) {
                     const uint32_t* qn = q + kWfsStride;  // the next set's runs
                     std::fprintf(stderr, "iter lane %zu t %3llu: carried %9llu (front %9u back %9u) camera %9llu shaded %9llu"
-                                 " [%u %u %u %u %u] ended %9llu -> next front %9u back %9u\n", l, (unsigned long long)t,
+                                 " [%u %u %u %u %u] fused %9llu ended %9llu -> next front %9u back %9u\n", l, (unsigned long long)t,
                                  (unsigned long long)old, q[cix(kCntFront)], q[cix(kCntBack)], (unsigned long long)live_new,
                                  (unsigned long long)shaded, q[cix(1)], q[cix(2)], q[cix(3)], q[cix(4)], q[cix(5)],
-                                 (unsigned long long)ended, qn[cix(kCntFront)], qn[cix(kCntBack)]);
+                                 (unsigned long long)fused, (unsigned long long)ended, qn[cix(kCntFront)], qn[cix(kCntBack)]);
                 }
 #endif
             }

@@ -180,6 +180,14 @@ constexpr int kExtAll = 0, kExtCarried = 1, kExtCamera = 2;
 // carried part runs at 5 waves: a C3-shaped frame (1920x1080x64, depth 50) 42.4 -> 41.1 ms
 // (profiles/r6/ab/ext_split_spheres_r6h5.jsonl; nest-0 example.sdl equal, so it keeps the merged launch)
 constexpr bool ext_split(int sm) { return sm == kSmNest2 || sm == kSmSpheres; }
+// The spheres mode's camera launch shades its hits of the lean classes (Lambertian, Metal, Dielectric) itself
+// instead of writing their records and queue entries for the shading launch (k_wfs_extend kFuse). The merged
+// launch (kExtAll) does not: the spheres mode always splits. RS_CAM_FUSE=0: the unfused kernel, for A/B (kernels
+// and host must be built with the same value).
+#ifndef RS_CAM_FUSE
+#define RS_CAM_FUSE 1
+#endif
+constexpr bool cam_fused(int sm, int part) { return RS_CAM_FUSE && sm == kSmSpheres && part == kExtCamera; }
 hipError_t launch_wfs_extend(const SceneRef& s, const DCamera& c, const PathParams& p, const WfState& w,
                              QEnt* const* queues, uint32_t it, const InjParams& inj, double* rad, uint32_t blocks,
                              int part, int sm, hipStream_t st, hipEvent_t ev0 = nullptr, hipEvent_t ev1 = nullptr);

@@ -1675,18 +1675,18 @@ __global__ __launch_bounds__(kBlock, LAMB ? RS_LAMB_WAVES : 1) void k_wf_shade(c
 constexpr int kClasses = kWfsClasses;
 constexpr int kClsLight = 6;
 
-// waves/SIMD the extend is bounded to: spheres and nest-0 scenes 4 (128 VGPRs; the spheres-mode
-// camera-ray extend 144 -> 128 VGPRs: bench frame 7.86 -> 7.63 ms; nest-0 129 -> 128: example.sdl
+// waves/SIMD the extend is bounded to: nest-0 scenes 4 (129 -> 128 VGPRs: example.sdl
 // 10.8 -> 10.3 ms; 5 waves spills and measured slower); nest-2 with the LDS image 3 (168 VGPRs, 184 B
 // of scratch: 4 % faster than 2 waves, 4 waves 12 % slower; profiles/r4/ab/nest2_registers; round 5 on the
 // C4-shaped frame: 2 waves 5.43 -> 4.54 Gseg/s, profiles/r5/ab/c4_waves_r5l), nest-2
 // with its tables in global memory 2 (its loads are L1 / L2 round trips that the spills would join)
-// The spheres mode's carried-path part (the divergent bounce >= 1 rays: lane efficiency 0.51 for BSDF rays,
-// profiles/r5/iters) at 5 waves: 96 VGPRs, 12 B of scratch, 5 blocks of 24 KiB stacks per CU; bench frame
-// 7.58 -> 7.31 ms. Its camera part keeps 4 (13 VGPRs would spill).
+// The spheres mode 5, every part: its unit is compiled without machine LICM and with sinking instead of spilling
+// (csrc/Makefile FLAGS_1). The batch bodies need 92-96 VGPRs; what used to take the camera part to 127 VGPRs + 12 B
+// of scratch at a 4-wave bound (and spill 108 B at 5) were loop invariants hoisted out of the grid-stride loop and
+// kept live across the body. Now: carried 92, camera 96 (with its in-place shading), merged 94, none with scratch;
+// 5 blocks of 27 KiB of LDS per CU (tools/regs.sh, tests/test_kernel_registers.py).
 constexpr int ext_min_waves(int sm, bool lobj = false, int part = kExtAll) {
-    if (sm == kSmSpheres && part == kExtCarried) return 5;
-    // (the spheres camera part at 5 waves spills 108 B: bench frame +4 %, profiles/r6/ab/waves_cam_lean_r7i.txt)
+    if (sm == kSmSpheres) return 5;
     return sm == kSmNest2 ? (lobj ? 3 : 2) : 4;
 }
 
@@ -1744,6 +1744,8 @@ __global__ __launch_bounds__(kBlock, ext_min_waves(SM, LOBJ, PART)) void k_wfs_e
     const uint32_t n = n_old + (PART == kExtCarried ? 0u : I.n_new);
     if (PART != kExtCamera && blockIdx.x == 0 && threadIdx.x == 0) cnt[0] = n_old;  // paths carried in (stats)
     const WfSet& cur = W.set[it & 1];
+    // the spheres mode's camera launch shades its lean-class hits in place (below)
+    constexpr bool kFuse = cam_fused(SM, PART);
     const uint32_t base0 = blockIdx.x * kBlock;
     for (uint32_t base = base0; base < n; base += gridDim.x * kBlock) {
         // thread -> record: the front run [0, nf), the back run from the set's end down, then the
@@ -1752,6 +1754,7 @@ __global__ __launch_bounds__(kBlock, ext_min_waves(SM, LOBJ, PART)) void k_wfs_e
         const bool gen = PART == kExtCamera || (PART == kExtAll && j >= n_old);
         const uint32_t i = gen ? nf + (j - n_old) : j < nf ? j : W.cap - 1u - (j - nf);
         int cls = -1, qbp = 0;
+        int fcls = -1;    // kFuse: the class of a hit shaded in this launch (then cls = -1: no queue entry)
         double qt = 0.0;  // the queue entry's hit (cls >= 0)
         bool live = false;
         Ray r;
@@ -1819,7 +1822,12 @@ __global__ __launch_bounds__(kBlock, ext_min_waves(SM, LOBJ, PART)) void k_wfs_e
                     // shading instead measured 0.5 % slower on the bench frame and 5 % on C4: profiles/r5/ab.)
                     qbp = bp;
                     qt = bend;
-                    if (gen) store_path(cur, i, r, v3(1.0, 1.0, 1.0), rng, item, 0u, W.tagw);
+                    if (kFuse && (cls == 0 || cls == 1 || cls == 3)) {  // shaded below, from registers: no record
+                        fcls = cls;
+                        cls = -1;
+                    } else if (gen) {
+                        store_path(cur, i, r, v3(1.0, 1.0, 1.0), rng, item, 0u, W.tagw);
+                    }
                     done = false;
                 }
             }
@@ -1852,6 +1860,43 @@ __global__ __launch_bounds__(kBlock, ext_min_waves(SM, LOBJ, PART)) void k_wfs_e
             QEnt q;
             q.i = i; q.bp = qbp; q.t = qt;
             queues[cls][slot] = q;
+        }
+        // Camera hits of the lean classes (Lambertian, Metal, Dielectric) are shaded here, as wfs_shade_batch would
+        // shade their level-0 records (T = 1): the wave holds the ray, the RNG, the winning prim and its t, so the
+        // 96-byte record, the queue entry and the shading launch's reads of both are not needed. Survivors go to
+        // the next set (level 1) through the next iteration's front / back counters, which this iteration's shading
+        // launches append to afterwards (same stream); the shaded samples are counted on word 1 of the block's
+        // statistics line. A class absent from the wave costs a skipped branch.
+        if constexpr (kFuse) {
+            bool alive = false;
+            int light_ray = 0;
+            V3 T = v3(1.0, 1.0, 1.0);
+            if (fcls >= 0) {
+                if (W.tagw) r.time = 0.0;  // what the record would have carried (load_path)
+                r.key = 0;
+                Hit h;
+                const DPrim Pr = S.prims[qbp];
+                sphere_rec_at(S.spheres[Pr.idx], Pr.mat, r, qt, h);
+                const int mi = h.mat >= 0 ? h.mat : S.default_mat;
+                const DMaterial& M0 = S.mats[mi];
+                bool cont;
+                if (fcls == 0) cont = shade_surface<RS_MAT_LAMBERTIAN, SM>(S, h, M0, M0, r, T, rng, &light_ray);
+                else if (fcls == 1) cont = shade_surface<RS_MAT_METAL, SM>(S, h, M0, M0, r, T, rng, &light_ray);
+                else cont = shade_surface<RS_MAT_DIELECTRIC, SM>(S, h, M0, M0, r, T, rng, &light_ray);
+                alive = cont && (1u < P.depth);  // the depth limit of ray_color (camera.rs:161)
+                if (!alive) {
+                    const V3 L = close_path(v3(0.0, 0.0, 0.0), T);
+                    put_rad(rad, item, L.x, L.y, L.z);
+                }
+            }
+            uint32_t* cnt_next = cnt + kWfsStride;
+            uint32_t* const gc[2] = {&cnt_next[cix(kCntBack)], &cnt_next[cix(kCntFront)]};
+            const uint32_t fslot = block_slot<2>(alive ? light_ray : -1, gc, fcls >= 0,
+                                                 &cnt[cix(kCntStat0 + (int)(blockIdx.x % kStatLines)) + 1]);
+            if (alive) {
+                const uint32_t p = light_ray ? fslot : W.cap - 1u - fslot;
+                store_path(W.set[(it + 1) & 1], p, r, T, rng, item, 1u, W.tagw);
+            }
         }
     }
 }
@@ -1991,8 +2036,13 @@ __device__ __forceinline__ void wfs_shade_batch(const DScene& S, const WfState& 
 template <int SM, bool G4, bool LOBJ, int PS>
 // (the nest-2 lean launch at 3 waves, no scratch: C4-shaped frame +0.4 %; at 5 waves +5.7 %:
 // profiles/r5/ab/n2_lean_waves_r6d.jsonl)
-// (the spheres lean launch at 5 waves spills 136 B: bench frame +10 %, profiles/r6/ab/waves_cam_lean_r7i.txt)
-#define RS_SHADE_WAVES(SM, G4, LOBJ, PS) (PS == 1 ? 4 : (SM == kSmNest2 && G4 && !LOBJ) ? 1 : 3)
+// The spheres unit (built without machine LICM, csrc/Makefile FLAGS_1): lean 100 VGPRs unbounded, 96 VGPRs + 20 B of
+// scratch at the 5-wave bound (RS_LEAN_WAVES; 4 and 5 measured equal on the bench frame, profiles/cam_fused/ab.txt);
+// heavy and unsplit 98-118 VGPRs at 4 waves (165 at 3 with the hoisting), no scratch.
+#ifndef RS_LEAN_WAVES
+#define RS_LEAN_WAVES 5
+#endif
+#define RS_SHADE_WAVES(SM, G4, LOBJ, PS) (SM == kSmSpheres ? (PS == 1 ? RS_LEAN_WAVES : 4) : PS == 1 ? 4 : (SM == kSmNest2 && G4 && !LOBJ) ? 1 : 3)
 __global__ __launch_bounds__(kBlock, RS_SHADE_WAVES(SM, G4, LOBJ, PS)) void k_wfs_shade_all(const DScene* __restrict__ Sp, WfState W,
                                                                                    QEnt* const* __restrict__ queues,
                                                                                    uint32_t class_mask, uint32_t it,
@@ -2013,6 +2063,15 @@ __global__ __launch_bounds__(kBlock, RS_SHADE_WAVES(SM, G4, LOBJ, PS)) void k_wf
         n[k] = ((class_mask & kPart) >> k & 1u) ? cnt[cix(1 + k)] : 0u;
         first[k + 1] = first[k] + (n[k] + kBlock - 1) / kBlock;
     }
+    // the iteration's queued paths (every class), next to its carried count: the host sizes the next same-shaped
+    // frame's shading grids from it (rs_host.cpp Slot::h_hist; spheres mode, the launch every iteration makes)
+    if constexpr (SM == kSmSpheres && PS != 2)
+        if (blockIdx.x == 0 && threadIdx.x == 0) {
+            uint32_t q = 0;
+#pragma unroll
+            for (int k = 0; k < kClasses; ++k) q += cnt[cix(1 + k)];
+            W.counts[(size_t)it * kWfsStride + 1] = q;
+        }
     for (uint32_t v = blockIdx.x; v < first[NC]; v += gridDim.x) {
         int k = 0;
 #pragma unroll

@@ -1,16 +1,18 @@
 #!/bin/bash
-# dev: build libraysnail_hip with extra -D flags into raysnail_amd/lib/var_<name>.so (the same
-# translation units as raysnail_amd/csrc/Makefile, compiled in parallel)
+# dev: build libraysnail_hip with extra flags into raysnail_amd/lib/var_<name>.so (the same translation
+# units and per-unit flags as raysnail_amd/csrc/Makefile, its unit-flags-<unit> target; compiled in parallel)
 # usage: tools/build_variant.sh <name> [flags...]
+#   NOUNIT=1: the Makefile's common flags for every unit (without its per-unit ones), for A/B of those
 set -e
 R=$(cd "$(dirname "$0")/.." && pwd)
 N=$1; shift
 B=/tmp/rs_var_$N; mkdir -p $B
-F="-O3 -std=c++17 -fPIC --offload-arch=gfx950 -ffp-contract=off -fno-fast-math $*"
-for t in -1 0 1 2 3 4; do
-  /opt/rocm/bin/hipcc $F -DRS_TU=$t -c $R/raysnail_amd/csrc/rs_kernels.hip -o $B/k$t.o &
+M="make -s --no-print-directory -C $R/raysnail_amd/csrc"
+for t in common 0 1 2 3 4; do
+  if [ -n "${NOUNIT:-}" ] && [ $t != common ]; then F="$($M unit-flags-common | sed 's/-DRS_TU=-1//') -DRS_TU=$t"; else F=$($M unit-flags-$t); fi
+  /opt/rocm/bin/hipcc $F "$@" -c $R/raysnail_amd/csrc/rs_kernels.hip -o $B/k$t.o &
 done
-/opt/rocm/bin/hipcc $F -x hip -c $R/raysnail_amd/csrc/rs_host.cpp -o $B/h.o &
+/opt/rocm/bin/hipcc $($M unit-flags-common | sed 's/-DRS_TU=-1//') "$@" -x hip -c $R/raysnail_amd/csrc/rs_host.cpp -o $B/h.o &
 wait
 /opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -o $R/raysnail_amd/lib/var_$N.so $B/k*.o $B/h.o
 echo built var_$N.so

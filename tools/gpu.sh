@@ -14,7 +14,7 @@
 #   scenes   kernel traces of the C4 / C5 scenes (tools/time_scene.py)
 #   configs  tools/bench_configs.py (C2-C5, X1, X2 vs the CPU oracle on row subsets)
 #   ab       bench.py of this tree against the baseline worktree base/, 3 rounds interleaved (tools/ab_report.py)
-#   variants bench.py of base/, the product and every raysnail_amd/lib/var_*.so (tools/build_variant.sh), 2 rounds
+#   variants bench.py of base/, the product and every raysnail_amd/lib/var_*.so (tools/build_variant.sh), REPS rounds (3)
 #   travstats per-category traversal counters (raysnail_amd/lib/trav_stats.so, a -DRS_TRAV_STATS build)
 #   abtrace  kernel traces of the bench frames, base/ then this tree (tools/trace_cmp.py)
 #   iters    per-iteration queue counts + extend / shading launches of the bench frame (dev library; tools/iter_table.py)
@@ -70,7 +70,8 @@ for s in "$@"; do
     (cd /tmp && step 240 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/tr_c4 -o tr -- python3 $R/tools/time_scene.py default quadric 16 50 1024x1024 > $OUT/tr_c4.log 2>&1) || { echo "c4 trace failed"; tail -5 $OUT/tr_c4.log; exit 1; }
     (cd /tmp && step 240 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/tr_c5 -o tr -- python3 $R/tools/time_scene.py default mesh 16 50 1920x1080 > $OUT/tr_c5.log 2>&1) || { echo "c5 trace failed"; tail -5 $OUT/tr_c5.log; exit 1; } ;;
   ab)
-    # this tree's bench line against the baseline worktree base/ (tools/ab_base.sh), 3 rounds interleaved
+    # this tree's bench line against the baseline checkout base/ (see `variants`), 3 rounds interleaved
+    [ -e $R/base/raysnail_amd/lib/libraysnail_hip.so ] || { echo "ab: no built baseline checkout in $R/base"; exit 1; }
     for rep in 1 2 3; do
       (cd $R/base && step 240 python3 bench.py $(full_of $R/base) --cpu-baseline 0 --steps 20 --warmup 5 > $OUT/ab_base_$rep.json 2> $OUT/ab_base.err) || { echo "base bench failed"; tail -5 $OUT/ab_base.err; exit 1; }
       (cd $R && step 240 python3 bench.py --full --cpu-baseline 0 --steps 20 --warmup 5 > $OUT/ab_new_$rep.json 2> $OUT/ab_new.err) || { echo "bench failed"; tail -5 $OUT/ab_new.err; exit 1; }
@@ -78,10 +79,15 @@ for s in "$@"; do
     (cd $R && python3 tools/ab_report.py $OUT/ab_base_*.json -- $OUT/ab_new_*.json | tee $OUT/ab.txt) ;;
   variants)
     # bench.py of base/, this tree's product and every dev variant (raysnail_amd/lib/var_*.so, tools/build_variant.sh),
-    # 2 rounds interleaved; frames of the variants are not checked here (dev bounds may be wrong on purpose)
-    B="--full --cpu-baseline 0 --steps 20 --warmup 5"
-    for rep in 1 2; do
-      if [ -d $R/base ]; then
+    # REPS rounds interleaved (default 3); frames of the variants are not checked here (dev bounds may be wrong on
+    # purpose). base/ is a built checkout of the commit compared against (git archive <commit> | tar -x -C base,
+    # then its build()); NOBASE=1 runs without one.
+    B="--full --cpu-baseline 0 --row-share 0 --steps 20 --warmup 5"
+    if [ -z "${NOBASE:-}" ] && [ ! -e $R/base/raysnail_amd/lib/libraysnail_hip.so ]; then
+      echo "variants: no built baseline checkout in $R/base (set NOBASE=1 to compare variants only)"; exit 1
+    fi
+    for rep in $(seq 1 ${REPS:-3}); do
+      if [ -z "${NOBASE:-}" ]; then
         (cd $R/base && step 240 python3 bench.py $(full_of $R/base) ${B#--full } > $OUT/v_base_$rep.json 2> $OUT/v.err) || { echo "base bench failed"; tail -5 $OUT/v.err; exit 1; }
       fi
       (cd $R && step 240 python3 bench.py $B > $OUT/v_prod_$rep.json 2> $OUT/v.err) || { echo "bench failed"; tail -5 $OUT/v.err; exit 1; }

@@ -10,13 +10,13 @@ from collections import defaultdict
 def main():
     log, trace = sys.argv[1], sys.argv[2]
     pat = re.compile(r"iter lane (\d+) t +(\d+): carried +(\d+) \(front +(\d+) back +(\d+)\) camera +(\d+) shaded +(\d+) "
-                     r"\[(\d+) (\d+) (\d+) (\d+) (\d+)\] ended +(\d+)")
+                     r"\[(\d+) (\d+) (\d+) (\d+) (\d+)\] (?:fused +(\d+) )?ended +(\d+)")
     frames, cur = [], []
     for line in open(log):
         m = pat.search(line)
         if not m:
             continue
-        v = [int(x) for x in m.groups()]
+        v = [int(x or 0) for x in m.groups()]  # (fused: absent in logs from before the camera launch shaded its hits)
         if v[1] == 0 and cur:
             frames.append(cur)
             cur = []
@@ -48,7 +48,7 @@ def main():
             per_it[t]["E"].append(es)
             per_it[t]["S"].append(sum(ss))
     counts = frames[-1] if frames else []
-    print(f"{'t':>2} {'front':>9} {'back':>9} {'camera':>9} {'shaded':>9} {'ended':>9} | {'ext front us':>12} {'ps/ray':>7} "
+    print(f"{'t':>2} {'front':>9} {'back':>9} {'camera':>9} {'shaded':>9} {'fused':>9} {'ended':>9} | {'ext front us':>12} {'ps/ray':>7} "
           f"{'ext rest us':>12} {'ps/ray':>7} {'shade us':>9} {'ps/path':>7}")
     tot = defaultdict(float)
     for t in sorted(per_it):
@@ -56,8 +56,8 @@ def main():
         k = len(es[0])
         ext = [sum(e[i] for e in es) / len(es) for i in range(k)]
         sh = sum(per_it[t]["S"]) / len(per_it[t]["S"])
-        c = counts[t] if t < len(counts) else [0] * 13
-        front, back, cam, shaded, ended = c[3], c[4], c[5], c[6], c[12]
+        c = counts[t] if t < len(counts) else [0] * 14
+        front, back, cam, shaded, fused, ended = c[3], c[4], c[5], c[6], c[12], c[13]
         if k == 2:
             ef, er = ext
             rest = back + cam
@@ -65,7 +65,7 @@ def main():
             ef, er = 0.0, ext[0]
             rest = front + back + cam
         tot["ef"] += ef; tot["er"] += er; tot["sh"] += sh
-        print(f"{t:>2} {front:>9} {back:>9} {cam:>9} {shaded:>9} {ended:>9} | {ef:>12.1f} {1e6 * ef / max(front, 1):>7.1f} "
+        print(f"{t:>2} {front:>9} {back:>9} {cam:>9} {shaded:>9} {fused:>9} {ended:>9} | {ef:>12.1f} {1e6 * ef / max(front, 1):>7.1f} "
               f"{er:>12.1f} {1e6 * er / max(rest, 1):>7.1f} {sh:>9.1f} {1e6 * sh / max(shaded, 1):>7.1f}")
     print(f"frame: extend front {tot['ef']:.1f} us, extend rest {tot['er']:.1f} us, shading {tot['sh']:.1f} us "
           f"({len(fl) - 1} frames averaged)")

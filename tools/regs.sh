@@ -1,8 +1,17 @@
 #!/bin/bash
-# dev: VGPRs / scratch / occupancy of kernels matching $1, with extra hipcc flags $2...
+# dev: VGPRs / scratch / occupancy of the kernels of one unit of rs_kernels.hip whose names match a pattern,
+# compiled with exactly the flags raysnail_amd/csrc/Makefile gives that unit (its unit-flags-<unit> target).
+# usage: tools/regs.sh <pattern> <unit: common | 0 .. 4> [extra hipcc flags ...]
+# one line per kernel: VGPRs scratch-bytes waves/SIMD name
+set -eu
 R=$(cd "$(dirname "$0")/.." && pwd)
-pat=$1; shift
-/opt/rocm/bin/hipcc -O3 -std=c++17 --offload-arch=gfx950 -ffp-contract=off "$@" -c $R/raysnail_amd/csrc/rs_kernels.hip -o /tmp/regs_$$.o -Rpass-analysis=kernel-resource-usage 2>&1 \
- | grep -E "remark: +(Function Name|VGPRs|ScratchSize|Occupancy)" | sed -E 's/.*remark: +//; s/ \[-Rpass.*//' \
- | awk -v p="$pat" '/Function Name/{n=$3; show=(n ~ p)} show && !/Function Name/{printf "%s %s  ", $1, $NF} /Occupancy/ && show {print n}'
-rm -f /tmp/regs_$$.o
+[ $# -ge 2 ] || { echo "usage: $0 <pattern> <unit: common | 0 .. 4> [extra hipcc flags ...]" >&2; exit 2; }
+pat=$1; unit=$2; shift 2
+HIPCC=${HIPCC:-/opt/rocm/bin/hipcc}
+flags=$(make -s --no-print-directory -C "$R/raysnail_amd/csrc" unit-flags-$unit)
+tmp=$(mktemp -d)
+trap 'rm -rf "$tmp"' EXIT
+$HIPCC $flags "$@" -c "$R/raysnail_amd/csrc/rs_kernels.hip" -o "$tmp/regs.o" -Rpass-analysis=kernel-resource-usage > "$tmp/log" 2>&1 \
+  || { cat "$tmp/log" >&2; exit 1; }
+grep -E "remark: +(Function Name|VGPRs|ScratchSize|Occupancy)" "$tmp/log" | sed -E 's/.*remark: +//; s/ \[-Rpass.*//' \
+  | awk -v p="$pat" '/Function Name/{n=$3; next} /^VGPRs:/{v=$NF} /^ScratchSize/{s=$NF} /^Occupancy/{if (n ~ p) print v, s, $NF, n}'
