@@ -12,6 +12,7 @@
 // correctly rounded ones of include/rs_crmath.h on both sides, so GPU frames equal the CPU
 // oracle's bit for bit.
 #include <cstdlib>
+#include <type_traits>
 
 #include <hip/hip_ext.h>
 
@@ -21,16 +22,22 @@
 // Translation units (Makefile): the scene-mode templates of the path kernels are compiled once per
 // mode, in parallel. RS_TU undefined: everything in one unit (tools/regs.sh, build_variant.sh);
 // RS_TU = -1: the common unit (mode-independent kernels, the launchers that dispatch on the scene
-// mode); RS_TU = k >= 0: scene mode k's launch_*_sm<k> instantiations only.
+// mode); RS_TU = k >= 0: scene mode k's launch_*_sm<k> instantiations only. RS_TU_SUFFIX names the
+// unit in its exported debug symbol (nothing, _c, _<k>).
+#define RS_PASTE_(a, b) a##b
+#define RS_PASTE(a, b) RS_PASTE_(a, b)
 #if !defined(RS_TU)
 #define RS_TU_COMMON 1
 #define RS_TU_MODES 1
+#define RS_TU_SUFFIX
 #elif RS_TU < 0
 #define RS_TU_COMMON 1
 #define RS_TU_MODES 0
+#define RS_TU_SUFFIX _c
 #else
 #define RS_TU_COMMON 0
 #define RS_TU_MODES 1
+#define RS_TU_SUFFIX RS_PASTE(_, RS_TU)
 #endif
 
 // the streaming (material-sorted) wavefront's scene modes (rs_internal.h streaming_mode)
@@ -65,6 +72,8 @@ typedef float f4v __attribute__((ext_vector_type(4)));
 typedef int i4v __attribute__((ext_vector_type(4)));
 typedef double d2v __attribute__((ext_vector_type(2)));
 #define RS_GLOBAL __attribute__((address_space(1)))
+// on a lambda handed to a walk as its per-leaf action: inlined like the __forceinline__ helpers
+#define RS_INLINE_LAMBDA __attribute__((always_inline))
 template <class T>
 __device__ __forceinline__ T gld(const void* base, uint32_t byte_off) {
     return *(const RS_GLOBAL T*)((const RS_GLOBAL char*)base + byte_off);
@@ -91,6 +100,47 @@ __device__ __forceinline__ void put_rad(double* __restrict__ rad, uint64_t item,
 __device__ unsigned long long g_trav_stats[4][32];
 #define RS_STAT(k, v) atomicAdd(&g_trav_stats[st_cat][k], (unsigned long long)(v))
 __shared__ int s_st_nodes[256], s_st_leaves[256], s_st_witer[256];
+// One ray's counters, threaded through the walks by reference: node steps, leaf tests, and the wave's leaf-loop
+// passes as this lane saw them. What a node step is differs by walk and is kept as recorded in profiles/:
+// traverse()'s in-order walk counts a box that passes, traverse_deferred every box test, bvh4_step a call,
+// the queued flat walk a node pass and a leaf pass.
+struct TravStat {
+    int nodes = 0, leaves = 0, witer = 0;
+    __device__ __forceinline__ void node() { ++nodes; }
+    __device__ __forceinline__ void leaf(int n = 1) { leaves += n; }
+    __device__ __forceinline__ void wave_pass() { ++witer; }
+    // leaf-loop passes of the wave at a node where this lane has nl leaves (the active lanes' maximum)
+    __device__ __forceinline__ void wave_leaf_passes(int nl) {
+        for (int q = 1; q <= 4; ++q) witer += __ballot(nl >= q) != 0ull;
+    }
+    // to the block's arrays, reduced per wave by the kernel (trav_stats_flush)
+    __device__ __forceinline__ void store() const {
+        s_st_nodes[threadIdx.x] = nodes;
+        s_st_leaves[threadIdx.x] = leaves;
+        s_st_witer[threadIdx.x] = witer;
+    }
+};
+// all 64 lanes converged: per ray sums, per wave the max node count (the wave runs the union of its
+// lanes' loops) and the wave's live lanes
+__device__ __forceinline__ void trav_stats_flush(bool live, int st_cat = 0) {
+    int n = live ? s_st_nodes[threadIdx.x] : 0, l = live ? s_st_leaves[threadIdx.x] : 0, mx = n, cnt = live ? 1 : 0;
+    for (int off = 32; off > 0; off >>= 1) {
+        n += __shfl_xor(n, off, 64); l += __shfl_xor(l, off, 64); cnt += __shfl_xor(cnt, off, 64);
+        mx = max(mx, __shfl_xor(mx, off, 64));
+    }
+    int wi = live ? s_st_witer[threadIdx.x] : 0;  // the wave's leaf-loop passes: the max over its lanes
+    for (int off = 32; off > 0; off >>= 1) wi = max(wi, __shfl_xor(wi, off, 64));
+    if ((threadIdx.x & 63) == 0 && cnt) { RS_STAT(0, n); RS_STAT(1, l); RS_STAT(2, cnt); RS_STAT(3, mx); RS_STAT(4, cnt); RS_STAT(5, 1); RS_STAT(6, wi); }
+    if (live) RS_STAT(8 + min(15, max(0, s_st_nodes[threadIdx.x]) / 8), 1);
+}
+#else
+struct TravStat {
+    __device__ __forceinline__ void node() {}
+    __device__ __forceinline__ void leaf(int = 1) {}
+    __device__ __forceinline__ void wave_pass() {}
+    __device__ __forceinline__ void wave_leaf_passes(int) {}
+    __device__ __forceinline__ void store() const {}
+};
 #endif
 
 // aabb.rs:20-38 with inv = 1/d[i] precomputed per ray (the reference recomputes the same value
@@ -437,31 +487,74 @@ __device__ __forceinline__ StkT<OVF, N> make_stk(const DScene& S, int* stk_all) 
     s.ovf_base = S.stk_ovf;
     return s;
 }
-#ifdef RS_TRAV_STATS
-// all 64 lanes converged: per ray sums, per wave the max node count (the wave runs the union of its
-// lanes' loops) and the wave's live lanes
-__device__ __forceinline__ void trav_stats_flush(bool live, int st_cat = 0) {
-    int n = live ? s_st_nodes[threadIdx.x] : 0, l = live ? s_st_leaves[threadIdx.x] : 0, mx = n, cnt = live ? 1 : 0;
-    for (int off = 32; off > 0; off >>= 1) {
-        n += __shfl_xor(n, off, 64); l += __shfl_xor(l, off, 64); cnt += __shfl_xor(cnt, off, 64);
-        mx = max(mx, __shfl_xor(mx, off, 64));
-    }
-    int wi = live ? s_st_witer[threadIdx.x] : 0;  // the wave's leaf-loop passes: the max over its lanes
-    for (int off = 32; off > 0; off >>= 1) wi = max(wi, __shfl_xor(wi, off, 64));
-    if ((threadIdx.x & 63) == 0 && cnt) { RS_STAT(0, n); RS_STAT(1, l); RS_STAT(2, cnt); RS_STAT(3, mx); RS_STAT(4, cnt); RS_STAT(5, 1); RS_STAT(6, wi); }
-    if (live) RS_STAT(8 + min(15, max(0, s_st_nodes[threadIdx.x]) / 8), 1);
+// A leaf (child code ~e names leaf entry e, rs_layout.h): test it and, when it is accepted, tighten the f32
+// range end of the box tests. The one place every walk's leaf tests go through.
+template <int SM, bool LOBJ = false>
+__device__ __forceinline__ void leaf_tighten(const DScene& S, int code, const Ray& r, const RayC& rc, double tmin,
+                                             double& best, double& bend, int& bp, float& best32) {
+    const int bp_prev = bp;
+    test_leaf<SM, LOBJ>(S, ~code, r, rc, tmin, best, bend, bp);
+    if (bp != bp_prev || bp >= 0) best32 = round_up_f(best);
 }
-#endif
+
+// The four child slots of one loaded 4-wide node for a ray. Per slot: the child code n, the entry e of
+// an inner child to visit (or -inf = not to visit), the code l of a leaf whose box is reached (or
+// INT32_MIN). Branch-free: all four boxes are tested (the node's loads issue together) and the slot
+// results are selects; an empty slot (INT32_MIN) is neither a leaf nor an inner child.
+struct Slots4 {
+    int n[4], l[4];
+    float e[4];
+    __device__ __forceinline__ int inner() const {
+        return (e[0] > -__builtin_huge_valf()) + (e[1] > -__builtin_huge_valf()) + (e[2] > -__builtin_huge_valf()) +
+               (e[3] > -__builtin_huge_valf());
+    }
+    __device__ __forceinline__ int leaves() const {
+        return (l[0] != INT32_MIN) + (l[1] != INT32_MIN) + (l[2] != INT32_MIN) + (l[3] != INT32_MIN);
+    }
+};
+__device__ __forceinline__ void test_slot(float nx, float ny, float nz, float fx, float fy, float fz, int c, const RayF4& rq,
+                                          float tmin32, float best32, int& n, float& e, int& l) {
+    float en;
+    const bool hk = slab4(nx, ny, nz, fx, fy, fz, rq, tmin32, best32, en) & (c != INT32_MIN);
+    l = (hk & (c < 0)) ? c : INT32_MIN;
+    n = c;
+    e = (hk & (c >= 0)) ? en : -__builtin_huge_valf();
+}
+__device__ __forceinline__ Slots4 test_slots4(const f4v& NX, const f4v& FX, const f4v& NY, const f4v& FY, const f4v& NZ,
+                                              const f4v& FZ, const i4v& NC, const RayF4& rq, float tmin32, float best32) {
+    Slots4 s;
+    test_slot(NX.x, NY.x, NZ.x, FX.x, FY.x, FZ.x, NC.x, rq, tmin32, best32, s.n[0], s.e[0], s.l[0]);
+    test_slot(NX.y, NY.y, NZ.y, FX.y, FY.y, FZ.y, NC.y, rq, tmin32, best32, s.n[1], s.e[1], s.l[1]);
+    test_slot(NX.z, NY.z, NZ.z, FX.z, FY.z, FZ.z, NC.z, rq, tmin32, best32, s.n[2], s.e[2], s.l[2]);
+    test_slot(NX.w, NY.w, NZ.w, FX.w, FY.w, FZ.w, NC.w, rq, tmin32, best32, s.n[3], s.e[3], s.l[3]);
+    return s;
+}
+__device__ __forceinline__ void cswap_desc(float& ea, int& na, float& eb, int& nb) {
+    if (eb > ea) { const float te = ea; ea = eb; eb = te; const int tn = na; na = nb; nb = tn; }
+}
+// A node with cnt > 0 inner children to visit: sort them descending by entry (farthest first, not-visited
+// last: 5 compare-swaps), push the cnt - 1 farther ones, return the nearest. Inside the LDS part of the
+// stack all three writes are issued (the ones above sp + cnt - 1 are dead), near its end only the live ones.
+template <class STK>
+__device__ __forceinline__ int sort_push4(Slots4& s, int cnt, int& sp, const STK& stk) {
+    cswap_desc(s.e[0], s.n[0], s.e[1], s.n[1]); cswap_desc(s.e[2], s.n[2], s.e[3], s.n[3]);
+    cswap_desc(s.e[0], s.n[0], s.e[2], s.n[2]); cswap_desc(s.e[1], s.n[1], s.e[3], s.n[3]);
+    cswap_desc(s.e[1], s.n[1], s.e[2], s.n[2]);
+    if (!STK::kOvf || sp + 3 <= STK::kN) {
+        stk.lds[sp * kBlock] = s.n[0];
+        stk.lds[(sp + 1) * kBlock] = s.n[1];
+        stk.lds[(sp + 2) * kBlock] = s.n[2];
+    } else {
+        if (cnt > 1) stk.put(sp, s.n[0]);
+        if (cnt > 2) stk.put(sp + 1, s.n[1]);
+        if (cnt > 3) stk.put(sp + 2, s.n[2]);
+    }
+    sp += cnt - 1;
+    return cnt == 1 ? s.n[0] : cnt == 2 ? s.n[1] : cnt == 3 ? s.n[2] : s.n[3];
+}
+
 // One node of the 4-wide near-first traversal: test the four child boxes of one 128-byte node,
 // push the farther inner children, test the node's leaves; returns the next node (-1: done).
-// Shared by traverse() and the persistent-lane flat-scene extend (k_wf_extend_pl).
-#ifdef RS_TRAV_STATS
-#define RS_ST_PARAMS , int& st_leaves, int& st_witer
-#define RS_ST_PASS , st_leaves, st_witer
-#else
-#define RS_ST_PARAMS
-#define RS_ST_PASS
-#endif
 // The spheres mode's tree top in LDS (TOP): the extend's blocks copy nodes 0 .. S.ltop - 1 of the breadth-first
 // tree here; a node step whose wave is entirely inside the top reads its node with ds_read (a wave-uniform choice,
 // so no lane waits on both paths), the others from the global copy.
@@ -469,19 +562,7 @@ __shared__ DNode4 s_top4[kLTop > 0 ? kLTop : 1];
 template <int SM, class STK, bool LOBJ = false, bool TOP = false>
 __device__ __forceinline__ int bvh4_step(const DScene& S, const Ray& r, const RayC& rc, const RayF4& rq, double tmin,
                                  float tmin32, int node, int& sp, const STK& stk, double& best, double& bend,
-                                 int& bp, float& best32 RS_ST_PARAMS) {
-#ifdef RS_TRAV_STATS
-#define RS_ST_LEAF4() ++st_leaves
-#else
-#define RS_ST_LEAF4()
-#endif
-#define RS_LEAF4(code)                                                         \
-    do {                                                                       \
-        RS_ST_LEAF4();                                                         \
-        const int bp_prev = bp;                                                \
-        test_leaf<SM, LOBJ>(S, ~(code), r, rc, tmin, best, bend, bp);          \
-        if (bp != bp_prev || bp >= 0) best32 = round_up_f(best);               \
-    } while (0)
+                                 int& bp, float& best32, TravStat& st) {
     f4v NX, FX, NY, FY, NZ, FZ;
     i4v NC;
     if (TOP && __ballot(node >= S.ltop) == 0ull) {
@@ -491,71 +572,31 @@ __device__ __forceinline__ int bvh4_step(const DScene& S, const Ray& r, const Ra
     } else {
         load_node4<LOBJ>(S, rq, node, NX, FX, NY, FY, NZ, FZ, NC);
     }
-    // per slot: inner-child code and entry (or -inf = not to visit); leaf codes are collected
-    // and tested after the four box tests, when the node's registers are dead. Branch-free:
-    // all four boxes are tested (the node's loads issue together) and the slot results are
-    // selects; an empty slot (INT32_MIN) is neither a leaf nor an inner child.
-    int n0, n1, n2, n3, l0, l1, l2, l3;
-    float e0, e1, e2, e3;
-#define RS_SLOT(K, NK, EK, LK)                                                                \
-    {                                                                                 \
-        float e;                                                                      \
-        const int c = NC.K;                                                           \
-        const bool hk = slab4(NX.K, NY.K, NZ.K, FX.K, FY.K, FZ.K, rq, tmin32, best32, e) & (c != INT32_MIN); \
-        LK = (hk & (c < 0)) ? c : INT32_MIN;                                          \
-        NK = c;                                                                       \
-        EK = (hk & (c >= 0)) ? e : -__builtin_huge_valf();                            \
-    }
-    RS_SLOT(x, n0, e0, l0) RS_SLOT(y, n1, e1, l1) RS_SLOT(z, n2, e2, l2) RS_SLOT(w, n3, e3, l3)
-#undef RS_SLOT
-#ifdef RS_TRAV_STATS
-    {   // leaf-loop passes of the wave at this node (the active lanes' maximum leaf count)
-        const int nl = (l0 != INT32_MIN) + (l1 != INT32_MIN) + (l2 != INT32_MIN) + (l3 != INT32_MIN);
-        for (int q = 1; q <= 4; ++q) st_witer += __ballot(nl >= q) != 0ull;
-    }
-#endif
-    const int cnt = (e0 > -__builtin_huge_valf()) + (e1 > -__builtin_huge_valf()) +
-                    (e2 > -__builtin_huge_valf()) + (e3 > -__builtin_huge_valf());
+    // leaf codes are collected and tested after the four box tests, when the node's registers are dead
+    Slots4 s = test_slots4(NX, FX, NY, FY, NZ, FZ, NC, rq, tmin32, best32);
+    st.wave_leaf_passes(s.leaves());
+    const int cnt = s.inner();
     int next = -1;
-    if (cnt > 0) {
-        // sort descending by entry (farthest first, not-visited last): 5 compare-swaps
-#define RS_CS(EA, NA, EB, NB) if (EB > EA) { const float te = EA; EA = EB; EB = te; const int tn = NA; NA = NB; NB = tn; }
-        RS_CS(e0, n0, e1, n1) RS_CS(e2, n2, e3, n3) RS_CS(e0, n0, e2, n2) RS_CS(e1, n1, e3, n3) RS_CS(e1, n1, e2, n2)
-#undef RS_CS
-        // the cnt - 1 farther children are pushed; inside the LDS part all three writes are
-        // issued (the ones above sp + cnt - 1 are dead), near its end only the live ones
-        if (!STK::kOvf || sp + 3 <= STK::kN) {
-            stk.lds[sp * kBlock] = n0;
-            stk.lds[(sp + 1) * kBlock] = n1;
-            stk.lds[(sp + 2) * kBlock] = n2;
-        } else {
-            if (cnt > 1) stk.put(sp, n0);
-            if (cnt > 2) stk.put(sp + 1, n1);
-            if (cnt > 3) stk.put(sp + 2, n2);
-        }
-        sp += cnt - 1;
-        next = cnt == 1 ? n0 : cnt == 2 ? n1 : cnt == 3 ? n2 : n3;
-    }
+    if (cnt > 0) next = sort_push4(s, cnt, sp, stk);
     // leaves of this node (their hits only shrink the range the next node is tested with),
     // in slot order through ONE copy of the leaf test: every lane tests its k-th leaf in
     // the same pass, so a wave runs max-over-lanes leaf tests per node, not one pass per
     // slot that any lane uses (one `if` per slot measured 2 % slower)
     while (true) {
         int code;
-        if (l0 != INT32_MIN) { code = l0; l0 = INT32_MIN; }
-        else if (l1 != INT32_MIN) { code = l1; l1 = INT32_MIN; }
-        else if (l2 != INT32_MIN) { code = l2; l2 = INT32_MIN; }
-        else if (l3 != INT32_MIN) { code = l3; l3 = INT32_MIN; }
+        if (s.l[0] != INT32_MIN) { code = s.l[0]; s.l[0] = INT32_MIN; }
+        else if (s.l[1] != INT32_MIN) { code = s.l[1]; s.l[1] = INT32_MIN; }
+        else if (s.l[2] != INT32_MIN) { code = s.l[2]; s.l[2] = INT32_MIN; }
+        else if (s.l[3] != INT32_MIN) { code = s.l[3]; s.l[3] = INT32_MIN; }
         else break;
-        RS_LEAF4(code);
+        st.leaf();
+        leaf_tighten<SM, LOBJ>(S, code, r, rc, tmin, best, bend, bp, best32);
     }
     if (cnt == 0 && sp > 0) {
         --sp;
         next = stk.get(sp);
     }
     return next;
-#undef RS_LEAF4
-#undef RS_ST_LEAF4
 }
 
 
@@ -577,110 +618,129 @@ __device__ __forceinline__ int bvh4_step(const DScene& S, const Ray& r, const Ra
 #define RS_LEAFQ_THR 48  // leaf pass at >= 48/64 of the working lanes with an entry queued (with the lane refill:
                          // 32 / 40 / 56 -> +0.8 / -0.1 / +1.9 % of the mesh extend, profiles/r5/ab/c5_leafq_thr_r6h.jsonl)
 #endif
-template <int SM, class STK>
+template <class STK>
 __device__ __forceinline__ int bvh4_node_q(const DScene& S, const RayF4& rq, float tmin32, float best32, int node, int& sp,
                                            const STK& stk, int* q, int& qt) {
     f4v NX, FX, NY, FY, NZ, FZ;
     i4v NC;
     load_node4(S, rq, node, NX, FX, NY, FY, NZ, FZ, NC);
-    int n0, n1, n2, n3, l0, l1, l2, l3;
-    float e0, e1, e2, e3;
-#define RS_SLOT(K, NK, EK, LK)                                                                \
-    {                                                                                 \
-        float e;                                                                      \
-        const int c = NC.K;                                                           \
-        const bool hk = slab4(NX.K, NY.K, NZ.K, FX.K, FY.K, FZ.K, rq, tmin32, best32, e) & (c != INT32_MIN); \
-        LK = (hk & (c < 0)) ? c : INT32_MIN;                                          \
-        NK = c;                                                                       \
-        EK = (hk & (c >= 0)) ? e : -__builtin_huge_valf();                            \
-    }
-    RS_SLOT(x, n0, e0, l0) RS_SLOT(y, n1, e1, l1) RS_SLOT(z, n2, e2, l2) RS_SLOT(w, n3, e3, l3)
-#undef RS_SLOT
+    Slots4 s = test_slots4(NX, FX, NY, FY, NZ, FZ, NC, rq, tmin32, best32);
     // the leaf entries, in slot order, to the lane's FIFO: four unconditional writes at the tail (the
     // caller guarantees four free entries), the tail advanced past the real ones
     {
         constexpr int M = RS_LEAFQ - 1;
         int k = qt;
-        q[(k & M) * kBlock] = l0; k += l0 != INT32_MIN;
-        q[(k & M) * kBlock] = l1; k += l1 != INT32_MIN;
-        q[(k & M) * kBlock] = l2; k += l2 != INT32_MIN;
-        q[(k & M) * kBlock] = l3; k += l3 != INT32_MIN;
+        q[(k & M) * kBlock] = s.l[0]; k += s.l[0] != INT32_MIN;
+        q[(k & M) * kBlock] = s.l[1]; k += s.l[1] != INT32_MIN;
+        q[(k & M) * kBlock] = s.l[2]; k += s.l[2] != INT32_MIN;
+        q[(k & M) * kBlock] = s.l[3]; k += s.l[3] != INT32_MIN;
         qt = k;
     }
-    const int cnt = (e0 > -__builtin_huge_valf()) + (e1 > -__builtin_huge_valf()) +
-                    (e2 > -__builtin_huge_valf()) + (e3 > -__builtin_huge_valf());
+    const int cnt = s.inner();
     int next;
     if (cnt == 0) {
         next = -1;
         if (sp > 0) { --sp; next = stk.get(sp); }
     } else {
-#define RS_CS(EA, NA, EB, NB) if (EB > EA) { const float te = EA; EA = EB; EB = te; const int tn = NA; NA = NB; NB = tn; }
-        RS_CS(e0, n0, e1, n1) RS_CS(e2, n2, e3, n3) RS_CS(e0, n0, e2, n2) RS_CS(e1, n1, e3, n3) RS_CS(e1, n1, e2, n2)
-#undef RS_CS
-        if (!STK::kOvf || sp + 3 <= STK::kN) {
-            stk.lds[sp * kBlock] = n0;
-            stk.lds[(sp + 1) * kBlock] = n1;
-            stk.lds[(sp + 2) * kBlock] = n2;
-        } else {
-            if (cnt > 1) stk.put(sp, n0);
-            if (cnt > 2) stk.put(sp + 1, n1);
-            if (cnt > 3) stk.put(sp + 2, n2);
-        }
-        sp += cnt - 1;
-        next = cnt == 1 ? n0 : cnt == 2 ? n1 : cnt == 3 ? n2 : n3;
+        next = sort_push4(s, cnt, sp, stk);
     }
     return next;
 }
 
-// World::hit of a flat scene with a 4-wide tree through queued leaf passes (above). q: this lane's
-// column of the block's FIFO array (RS_LEAFQ x kBlock ints). Every lane of the wave that calls it
-// must call it (the pass choice is a ballot over the calling lanes).
+// One ray's state in the queued walk: the node to step next (-1: none left), the stack and FIFO cursors and
+// the hit so far. q: the lane's column of the block's FIFO array (RS_LEAFQ x kBlock ints).
+struct FlatWalk {
+    int node, sp, qh, qt, bp;
+    double best, bend;
+    float best32;
+    __device__ __forceinline__ void reset(int root) {
+        best = RS_INF; bend = RS_INF; best32 = __builtin_huge_valf();
+        bp = -1; node = root; sp = 0; qh = 0; qt = 0;
+    }
+    __device__ __forceinline__ bool idle() const { return node < 0 && qt == qh; }
+    __device__ __forceinline__ bool busy() const { return node >= 0 || qt != qh; }
+    // the winner's prim handle (leaf entry -> prim)
+    __device__ __forceinline__ int prim(const DScene& S) const { return (bp >= 0 && S.lprim) ? S.lprim[bp] : bp; }
+};
+// One wave pass of the queued walk (above) over the calling lanes' states; the caller loops while a lane is busy
+// (__ballot(w.busy()), the pass's `work`). rc_of() gives the leaf tests' ray constants: the caller decides whether
+// they stay live across passes.
+template <int SM, class STK, class RCOF>
+__device__ __forceinline__ void flat_q_pass(const DScene& S, const Ray& r, const RayF4& rq, double tmin, float tmin32,
+                                            FlatWalk& w, const STK& stk, int* q, RCOF rc_of, TravStat& st) {
+    const bool has_leaf = w.qt != w.qh;
+    const bool can_node = w.node >= 0 && w.qt - w.qh <= RS_LEAFQ - 4;
+    const uint64_t work = __ballot(w.busy());
+    const uint64_t lm = __ballot(has_leaf);
+    if (__popcll(lm) * 64 >= RS_LEAFQ_THR * __popcll(work) || __ballot(can_node) == 0ull) {
+        st.wave_pass();
+        if (has_leaf) {
+            const int code = q[(w.qh & (RS_LEAFQ - 1)) * kBlock];
+            ++w.qh;
+            st.leaf();
+            leaf_tighten<SM>(S, code, r, rc_of(), tmin, w.best, w.bend, w.bp, w.best32);
+        }
+    } else if (can_node) {
+        st.node();
+        w.node = bvh4_node_q(S, rq, tmin32, w.best32, w.node, w.sp, stk, q, w.qt);
+    }
+}
+
+// World::hit of a flat scene with a 4-wide tree through queued leaf passes (above). Every lane of the
+// wave that calls it must call it (the pass choice is a ballot over the calling lanes).
 template <int SM, class STK>
 __device__ __forceinline__ int traverse_flat_q(const DScene& S, const Ray& r, double tmin, double& bend_out, const STK& stk,
                                                int* q) {
     const RayC rc = ray_consts(r);
     const RayF4 rq = make_rayf4(make_rayf(r.o, rc.inv));
     const float tmin32 = -round_up_f(-tmin);
-    double best = RS_INF, bend = RS_INF;
-    float best32 = __builtin_huge_valf();
-    int bp = -1, node = S.root4, sp = 0, qh = 0, qt = 0;
-#ifdef RS_TRAV_STATS
-    int st_nodes = 0, st_leaves = 0, st_witer = 0;
-#endif
+    FlatWalk w;
+    w.reset(S.root4);
+    TravStat st;
+    while (__ballot(w.busy()) != 0ull)
+        flat_q_pass<SM>(S, r, rq, tmin, tmin32, w, stk, q, [&]() RS_INLINE_LAMBDA -> const RayC& { return rc; }, st);
+    st.store();
+    bend_out = w.bend;
+    return w.prim(S);
+}
+
+// The in-order 4-wide tree (rs_host.cpp collapse4_inorder) walked in BVH::hit's recursion order: the slots of
+// a node left to right, each child's box tested when it is reached, with the range end tend32 as it is then
+// (read through the reference: on_leaf may tighten it); entering an inner child pushes (node, next slot).
+// on_leaf(c) is called, at one site, for each leaf whose box is reached. ALLBOX: the statistics count every box
+// test as a node step (the deferred walk's records) instead of every box that passes (traverse()'s).
+template <bool LOBJ, bool ALLBOX, class STK, class LEAF>
+__device__ __forceinline__ void walk4_inorder(const DScene& S, const RayF& rf, float tmin32, const float& tend32,
+                                              const STK& stk, TravStat& st, LEAF on_leaf) {
+    int k = 0, node = S.root4, sp = 0;
     while (true) {
-        const bool has_leaf = qt != qh;
-        const bool can_node = node >= 0 && qt - qh <= RS_LEAFQ - 4;
-        const uint64_t work = __ballot(node >= 0 || has_leaf);
-        if (work == 0ull) break;
-        const uint64_t lm = __ballot(has_leaf);
-        if (__popcll(lm) * 64 >= RS_LEAFQ_THR * __popcll(work) || __ballot(can_node) == 0ull) {
-#ifdef RS_TRAV_STATS
-            ++st_witer;
-#endif
-            if (has_leaf) {
-                const int code = q[(qh & (RS_LEAFQ - 1)) * kBlock];
-                ++qh;
-#ifdef RS_TRAV_STATS
-                ++st_leaves;
-#endif
-                const int bp_prev = bp;
-                test_leaf<SM>(S, ~code, r, rc, tmin, best, bend, bp);
-                if (bp != bp_prev || bp >= 0) best32 = round_up_f(best);
+        const uint32_t nb = (uint32_t)node * (uint32_t)sizeof(DNode4) + 4u * (uint32_t)k;
+        const int c = nld<LOBJ, int>(S.nodes4, nb + 96u);
+        if (c != INT32_MIN) {  // (slots are filled from the left: at an empty one the node is done)
+            const float lo[3] = {nld<LOBJ, float>(S.nodes4, nb), nld<LOBJ, float>(S.nodes4, nb + 16u),
+                                 nld<LOBJ, float>(S.nodes4, nb + 32u)};
+            const float hi[3] = {nld<LOBJ, float>(S.nodes4, nb + 48u), nld<LOBJ, float>(S.nodes4, nb + 64u),
+                                 nld<LOBJ, float>(S.nodes4, nb + 80u)};
+            float e;
+            if (ALLBOX) st.node();
+            if (slab32(lo, hi, rf, tmin32, tend32, e)) {
+                if (!ALLBOX) st.node();
+                if (c < 0) {
+                    on_leaf(c);
+                } else {
+                    if (k < 3) { stk.put(sp, node * 4 + k + 1); ++sp; }  // come back for the next slot
+                    node = c;
+                    k = 0;
+                    continue;
+                }
             }
-        } else if (can_node) {
-#ifdef RS_TRAV_STATS
-            ++st_nodes;
-#endif
-            node = bvh4_node_q<SM>(S, rq, tmin32, best32, node, sp, stk, q, qt);
+            if (k < 3) { ++k; continue; }
         }
+        if (sp == 0) break;
+        --sp;
+        const int v = stk.get(sp);
+        node = v >> 2; k = v & 3;
     }
-#ifdef RS_TRAV_STATS
-    s_st_nodes[threadIdx.x] = st_nodes;
-    s_st_leaves[threadIdx.x] = st_leaves;
-    s_st_witer[threadIdx.x] = st_witer;
-#endif
-    bend_out = bend;
-    return (bp >= 0 && S.lprim) ? S.lprim[bp] : bp;
 }
 
 // World::hit in BVH::hit's recursion order (bvh.rs:173-192) on the in-order 4-wide tree with the leaf
@@ -702,49 +762,16 @@ __device__ __forceinline__ int traverse_deferred(const DScene& S, const Ray& r, 
     double best = RS_INF, bend = RS_INF;
     int bp = -1;
     uint32_t skip = 0;
-#ifdef RS_TRAV_STATS
-    int st_nodes = 0, st_leaves = 0;
-#endif
+    TravStat st;
     while (true) {
         uint32_t found = 0;  // leaves met by this walk; slots skip .. skip + K - 1 are listed
         {
             const RayF rf = make_rayf(r.o, rc.inv);
-            int k = 0, node = S.root4, sp = 0;
-            while (true) {
-                const uint32_t nb = (uint32_t)node * (uint32_t)sizeof(DNode4) + 4u * (uint32_t)k;
-                const int c = nld<true, int>(S.nodes4, nb + 96u);
-                if (c == INT32_MIN) {  // slots are filled from the left: the node is done
-                    if (sp == 0) break;
-                    --sp;
-                    const int v = stk.get(sp);
-                    node = v >> 2; k = v & 3;
-                    continue;
-                }
-                const float lo[3] = {nld<true, float>(S.nodes4, nb), nld<true, float>(S.nodes4, nb + 16u),
-                                     nld<true, float>(S.nodes4, nb + 32u)};
-                const float hi[3] = {nld<true, float>(S.nodes4, nb + 48u), nld<true, float>(S.nodes4, nb + 64u),
-                                     nld<true, float>(S.nodes4, nb + 80u)};
-                float e;
-#ifdef RS_TRAV_STATS
-                ++st_nodes;  // (deferred walk: box tests)
-#endif
-                if (slab32(lo, hi, rf, tmin32, __builtin_huge_valf(), e)) {
-                    if (c < 0) {
-                        if (found >= skip && found - skip < K) q[(found - skip) * kBlock] = c;
-                        ++found;
-                    } else {
-                        if (k < 3) { stk.put(sp, node * 4 + k + 1); ++sp; }  // come back for the next slot
-                        node = c;
-                        k = 0;
-                        continue;
-                    }
-                }
-                if (k < 3) { ++k; continue; }
-                if (sp == 0) break;
-                --sp;
-                const int v = stk.get(sp);
-                node = v >> 2; k = v & 3;
-            }
+            const float tend32 = __builtin_huge_valf();
+            walk4_inorder<true, true>(S, rf, tmin32, tend32, stk, st, [&found, skip, q](int c) RS_INLINE_LAMBDA {
+                if (found >= skip && found - skip < K) q[(found - skip) * kBlock] = c;
+                ++found;
+            });
         }
         const uint32_t m = found > skip ? min(found - skip, K) : 0u;
 #ifndef RS_NO_KIND_MAJOR
@@ -772,17 +799,11 @@ __device__ __forceinline__ int traverse_deferred(const DScene& S, const Ray& r, 
         } else
 #endif
         for (uint32_t i = 0; i < m; ++i) test_leaf<SM, true>(S, ~q[i * kBlock], r, rc, tmin, best, bend, bp);
-#ifdef RS_TRAV_STATS
-        st_leaves += (int)m;
-#endif
+        st.leaf((int)m);
         if (found <= skip + K) break;
         skip += K;
     }
-#ifdef RS_TRAV_STATS
-    s_st_nodes[threadIdx.x] = st_nodes;
-    s_st_leaves[threadIdx.x] = st_leaves;
-    s_st_witer[threadIdx.x] = 0;
-#endif
+    st.store();
     bend_out = bend;
     return bp;  // nest modes' leaf codes name prims (no lprim)
 }
@@ -805,71 +826,23 @@ __device__ __forceinline__ int traverse(const DScene& S, const Ray& r, double tm
     double best = RS_INF, bend = RS_INF;
     float best32 = __builtin_huge_valf();
     int bp = -1;
-    int node = S.root;
-    int sp = 0;
-#ifdef RS_TRAV_STATS
-    int st_nodes = 0, st_leaves = 0, st_witer = 0;
-#define RS_ST_NODE() ++st_nodes
-#define RS_ST_LEAF() ++st_leaves
-#else
-#define RS_ST_NODE()
-#define RS_ST_LEAF()
-#endif
-// a leaf: child code ~e names leaf entry e (rs_layout.h)
-#define RS_LEAF(code)                                                          \
-    do {                                                                       \
-        RS_ST_LEAF();                                                          \
-        const int bp_prev = bp;                                                \
-        test_leaf<SM, LOBJ>(S, ~(code), r, rc, tmin, best, bend, bp);          \
-        if (bp != bp_prev || bp >= 0) best32 = round_up_f(best);               \
-    } while (0)
+    TravStat st;
     // (the generic mode carries it too: its kernels include the World::hit probe, k_probe_hit, which
     // serves every scene mode's trees)
     if ((SM == kSmNest0 || SM == kSmNest2 || SM == kSmGeneric) && S.root4 >= 0 && S.ref_order) {
-        // BVH::hit's recursion order on the in-order 4-wide tree (rs_host.cpp collapse4_inorder): the
-        // slots of a node left to right, each child's box tested when it is reached with the range the
-        // slots before it left behind; entering an inner child pushes (node, next slot).
-        int k = 0;
-        node = S.root4;
-        while (true) {
-            const uint32_t nb = (uint32_t)node * (uint32_t)sizeof(DNode4) + 4u * (uint32_t)k;
-            const int c = nld<LOBJ, int>(S.nodes4, nb + 96u);
-            if (c == INT32_MIN) {  // slots are filled from the left: the node is done
-                if (sp == 0) break;
-                --sp;
-                const int v = stk.get(sp);
-                node = v >> 2; k = v & 3;
-                continue;
-            }
-            const float lo[3] = {nld<LOBJ, float>(S.nodes4, nb), nld<LOBJ, float>(S.nodes4, nb + 16u),
-                                 nld<LOBJ, float>(S.nodes4, nb + 32u)};
-            const float hi[3] = {nld<LOBJ, float>(S.nodes4, nb + 48u), nld<LOBJ, float>(S.nodes4, nb + 64u),
-                                 nld<LOBJ, float>(S.nodes4, nb + 80u)};
-            float e;
-            if (slab32(lo, hi, rf, tmin32, best32, e)) {
-                RS_ST_NODE();
-                if (c < 0) {
-                    RS_LEAF(c);
-                } else {
-                    if (k < 3) { stk.put(sp, node * 4 + k + 1); ++sp; }  // come back for the next slot
-                    node = c;
-                    k = 0;
-                    continue;
-                }
-            }
-            if (k < 3) { ++k; continue; }
-            if (sp == 0) break;
-            --sp;
-            const int v = stk.get(sp);
-            node = v >> 2; k = v & 3;
-        }
+        // BVH::hit's recursion order on the in-order 4-wide tree, each leaf tested when its box is reached: the
+        // boxes after it see the range it left behind
+        walk4_inorder<LOBJ, false>(S, rf, tmin32, best32, stk, st, [&](int c) RS_INLINE_LAMBDA {
+            st.leaf();
+            leaf_tighten<SM, LOBJ>(S, c, r, rc, tmin, best, bend, bp, best32);
+        });
     } else if (S.root4 >= 0 && !S.ref_order) {
         // 4-wide near-first (bvh4_step): nearest inner child next, the rest pushed far-to-near
         const RayF4 rq = make_rayf4(rf);
-        node = S.root4;
+        int node = S.root4, sp = 0;
         while (node >= 0) {
-            RS_ST_NODE();
-            node = bvh4_step<SM, STK, LOBJ, TOP>(S, r, rc, rq, tmin, tmin32, node, sp, stk, best, bend, bp, best32 RS_ST_PASS);
+            st.node();
+            node = bvh4_step<SM, STK, LOBJ, TOP>(S, r, rc, rq, tmin, tmin32, node, sp, stk, best, bend, bp, best32, st);
         }
     } else {
         // (the generic mode's reference-order scenes: boxes / quadrics / CSG in rich scenes) BVH::hit's
@@ -877,14 +850,15 @@ __device__ __forceinline__ int traverse(const DScene& S, const Ray& r, double tm
         // k = 1 the right one (its box tested with the range the left subtree left behind); an inner
         // left child is entered with the node pushed to come back for its right child. One leaf-test
         // site, so the nested-object tests are inlined once.
-        int k = 0;
+        int k = 0, node = S.root, sp = 0;
         while (true) {
             const DNode& N = S.nodes[node];
             const int c = N.child[k];
             float e;
             if (c != INT32_MIN && slab32(N.lo[k], N.hi[k], rf, tmin32, best32, e)) {
                 if (c < 0) {
-                    RS_LEAF(c);
+                    st.leaf();
+                    leaf_tighten<SM, LOBJ>(S, c, r, rc, tmin, best, bend, bp, best32);
                 } else {
                     if (k == 0) { stk.put(sp, node); ++sp; }  // come back for the right child
                     node = c;
@@ -899,12 +873,7 @@ __device__ __forceinline__ int traverse(const DScene& S, const Ray& r, double tm
             k = 1;
         }
     }
-#undef RS_LEAF
-#ifdef RS_TRAV_STATS
-    s_st_nodes[threadIdx.x] = st_nodes;   // reduced per wave by the kernel (rs_trav_stats_flush)
-    s_st_leaves[threadIdx.x] = st_leaves;
-    s_st_witer[threadIdx.x] = st_witer;
-#endif
+    st.store();
     bend_out = TOUT ? best : bend;
     return (bp >= 0 && S.lprim) ? S.lprim[bp] : bp;
 }
@@ -1542,17 +1511,18 @@ __global__ __launch_bounds__(kBlock, kWfExtFlatWaves) void k_wf_extend_dyn(const
     // the wave's pool of drawn records [pa, pa + pn) (wave-uniform), its shard, shards found empty
     uint32_t pa = 0, pn = 0;
     uint32_t ck = blockIdx.x % kFetchCounters, tries = 0;
-    int i = -1, bp = -1, node = -1, sp = 0, qh = 0, qt = 0;
+    int i = -1;
     Ray r;
     r.o = r.d = v3(0.0, 0.0, 0.0);
     r.time = 0.0;
     RayF4 rq = make_rayf4(make_rayf(r.o, r.o));
-    double best = RS_INF, bend = RS_INF;
-    float best32 = __builtin_huge_valf();
+    FlatWalk w;
+    w.reset(-1);
+    TravStat st;  // (unused: this kernel reports no counters)
     while (true) {
-        const bool idle = node < 0 && qt == qh;
+        const bool idle = w.idle();
         if (idle && i >= 0) {
-            W.hit[i] = make_double2(__longlong_as_double((long long)((bp >= 0 && S.lprim) ? S.lprim[bp] : bp)), bend);
+            W.hit[i] = make_double2(__longlong_as_double((long long)w.prim(S)), w.bend);
             i = -1;
         }
         const uint64_t im = __ballot(idle);
@@ -1582,29 +1552,15 @@ __global__ __launch_bounds__(kBlock, kWfExtFlatWaves) void k_wf_extend_dyn(const
                     i = (int)j;
                     r = load_ray(cur, j, W.tagw);
                     rq = make_rayf4(make_rayf(r.o, v3(1.0 / r.d.x, 1.0 / r.d.y, 1.0 / r.d.z)));
-                    best = RS_INF; bend = RS_INF; best32 = __builtin_huge_valf();
-                    bp = -1; node = S.root4; sp = 0; qh = 0; qt = 0;
+                    w.reset(S.root4);
                 }
             }
             if (ni <= pn) { pa += ni; pn -= ni; }
             else { const uint32_t u = min(ni - pn, pbn); pa = pb + u; pn = pbn - u; }
         }
-        const bool has_leaf = qt != qh;
-        const bool can_node = node >= 0 && qt - qh <= RS_LEAFQ - 4;
-        const uint64_t work = __ballot(node >= 0 || has_leaf);
-        if (work == 0ull) break;  // every lane idle after a refill attempt: pool and shards are empty
-        const uint64_t lm = __ballot(has_leaf);
-        if (__popcll(lm) * 64 >= RS_LEAFQ_THR * __popcll(work) || __ballot(can_node) == 0ull) {
-            if (has_leaf) {
-                const int code = q[(qh & (RS_LEAFQ - 1)) * kBlock];
-                ++qh;
-                const int bp_prev = bp;
-                test_leaf<SM>(S, ~code, r, ray_consts(r), tmin, best, bend, bp);
-                if (bp != bp_prev || bp >= 0) best32 = round_up_f(best);
-            }
-        } else if (can_node) {
-            node = bvh4_node_q<SM>(S, rq, tmin32, best32, node, sp, stk, q, qt);
-        }
+        if (__ballot(w.busy()) == 0ull) break;  // every lane idle after a refill attempt: pool and shards are empty
+        // the ray constants are computed inside the leaf pass, so no RayC stays live across the refill
+        flat_q_pass<SM>(S, r, rq, tmin, tmin32, w, stk, q, [&]() RS_INLINE_LAMBDA { return ray_consts(r); }, st);
     }
 }
 
@@ -2346,37 +2302,44 @@ hipError_t wf_occupancy_sm(int* e, int* sh) {
 // modes keep one instantiation each: compile time)
 [[maybe_unused]] static inline bool lds_only_stack(const SceneRef& s, int sm) { return s.host->stack_need + 3 <= stack_lds(sm); }
 
+// A launcher's runtime choices as compile-time constants. with_bool<CAN>(b, f): f(std::true_type) when b and
+// the mode compiles that case (CAN), else f(std::false_type) -- a mode instantiates only the kernels it can run
+// (compile time, code size). with_part: the extend's part; the nest-2 mode runs split launches only (ext_split).
+template <bool CAN, class F>
+static inline void with_bool(bool b, F&& f) {
+    if constexpr (CAN) {
+        if (b) { f(std::true_type{}); return; }
+    }
+    f(std::false_type{});
+}
+template <int SMC, class F>
+static inline void with_part(int part, F&& f) {
+    if constexpr (SMC != kSmNest2) {
+        if (part == kExtAll) { f(std::integral_constant<int, kExtAll>{}); return; }
+    }
+    if (part == kExtCamera) f(std::integral_constant<int, kExtCamera>{});
+    else f(std::integral_constant<int, kExtCarried>{});
+}
+constexpr bool nest_mode(int sm) { return sm == kSmNest0 || sm == kSmNest2; }
+
 template <int SMC>
 hipError_t wfs_extend_sm(const SceneRef& s, const DCamera& c, const PathParams& p, const WfState& w, QEnt* const* queues,
                          uint32_t it, const InjParams& inj, double* rad, uint32_t blocks, int part, hipStream_t st,
                          hipEvent_t ev0, hipEvent_t ev1) {
     if (!blocks) return hipSuccess;
-#define RS_EXT_LAUNCH(OVF, PART) RS_EXT_LAUNCH_L(OVF, PART, false, 0)
-#define RS_EXT_LAUNCH_L(OVF, PART, LOBJ, SHM)                                                                        \
-    hipExtLaunchKernelGGL((k_wfs_extend<SMC, OVF, PART, LOBJ>), dim3(blocks), dim3(kBlock), SHM, st, ev0, ev1, 0, s.dev, \
-                          w, queues, it, rad, c, p, inj)
     // nest modes: the LDS image when the scene has one (the spheres mode has none: its 41 KB tree and
-    // sphere records per block halved the extend's occupancy, bench frame 7.63 -> 9.94 ms)
+    // sphere records per block halved the extend's occupancy, bench frame 7.63 -> 9.94 ms). Spheres mode:
+    // the LDS-only stack where the tree allows it.
     const uint32_t shm = s.host->limg_bytes;
-    if constexpr (SMC == kSmNest2) {  // split launches only (ext_split)
-        if (part == kExtCamera) { if (shm) RS_EXT_LAUNCH_L(true, kExtCamera, true, shm); else RS_EXT_LAUNCH(true, kExtCamera); }
-        else { if (shm) RS_EXT_LAUNCH_L(true, kExtCarried, true, shm); else RS_EXT_LAUNCH(true, kExtCarried); }
-    } else if constexpr (SMC == kSmNest0) {
-        if (part == kExtAll) { if (shm) RS_EXT_LAUNCH_L(true, kExtAll, true, shm); else RS_EXT_LAUNCH(true, kExtAll); }
-        else if (part == kExtCamera) { if (shm) RS_EXT_LAUNCH_L(true, kExtCamera, true, shm); else RS_EXT_LAUNCH(true, kExtCamera); }
-        else { if (shm) RS_EXT_LAUNCH_L(true, kExtCarried, true, shm); else RS_EXT_LAUNCH(true, kExtCarried); }
-    } else if constexpr (SMC == kSmSpheres) {
-        const bool lds = lds_only_stack(s, SMC);
-        if (part == kExtAll) { if (lds) RS_EXT_LAUNCH(false, kExtAll); else RS_EXT_LAUNCH(true, kExtAll); }
-        else if (part == kExtCamera) { if (lds) RS_EXT_LAUNCH(false, kExtCamera); else RS_EXT_LAUNCH(true, kExtCamera); }
-        else { if (lds) RS_EXT_LAUNCH(false, kExtCarried); else RS_EXT_LAUNCH(true, kExtCarried); }
-    } else {
-        if (part == kExtAll) RS_EXT_LAUNCH(true, kExtAll);
-        else if (part == kExtCamera) RS_EXT_LAUNCH(true, kExtCamera);
-        else RS_EXT_LAUNCH(true, kExtCarried);
-    }
-#undef RS_EXT_LAUNCH
-#undef RS_EXT_LAUNCH_L
+    with_part<SMC>(part, [&](auto part_c) {
+        with_bool<nest_mode(SMC)>(shm != 0, [&](auto lobj) {
+            with_bool<SMC == kSmSpheres>(lds_only_stack(s, SMC), [&](auto lds) {
+                hipExtLaunchKernelGGL((k_wfs_extend<SMC, !decltype(lds)::value, decltype(part_c)::value, decltype(lobj)::value>),
+                                      dim3(blocks), dim3(kBlock), decltype(lobj)::value ? shm : 0, st, ev0, ev1, 0, s.dev, w,
+                                      queues, it, rad, c, p, inj);
+            });
+        });
+    });
     return hipGetLastError();
 }
 
@@ -2385,13 +2348,10 @@ hipError_t wfs_finish_sm(const SceneRef& s, const WfState& w, uint32_t it, uint3
                          hipStream_t st) {
     if (!blocks) return hipSuccess;
     const uint32_t shm = s.host->limg_bytes;  // nest modes' LDS image
-    if constexpr (SMC == kSmNest0 || SMC == kSmNest2) {
-        if (shm) {
-            hipLaunchKernelGGL((k_wfs_finish<SMC, true>), dim3(blocks), dim3(kBlock), shm, st, s.dev, w, it, depth, rad);
-            return hipGetLastError();
-        }
-    }
-    hipLaunchKernelGGL((k_wfs_finish<SMC, false>), dim3(blocks), dim3(kBlock), 0, st, s.dev, w, it, depth, rad);
+    with_bool<nest_mode(SMC)>(shm != 0, [&](auto lobj) {
+        hipLaunchKernelGGL((k_wfs_finish<SMC, decltype(lobj)::value>), dim3(blocks), dim3(kBlock),
+                           decltype(lobj)::value ? shm : 0, st, s.dev, w, it, depth, rad);
+    });
     return hipGetLastError();
 }
 
@@ -2399,37 +2359,28 @@ template <int SMC>
 hipError_t wfs_shade_all_sm(const SceneRef& s, const WfState& w, QEnt* const* queues, uint32_t class_mask, uint32_t it,
                             uint32_t depth, double* rad, uint32_t blocks, bool split, hipStream_t st) {
     if (!blocks) return hipSuccess;
-#define RS_SHADE_LAUNCH(G4, LOBJ, PS, SHM)                                                                          \
-    hipLaunchKernelGGL((k_wfs_shade_all<SMC, G4, LOBJ, PS>), dim3(blocks), dim3(kBlock), SHM, st, s.dev, w, queues, \
-                       class_mask, it, depth, rad)
     const uint32_t shm = s.host->limg_bytes;  // nest modes' LDS image (none in the spheres mode)
-    if constexpr (SMC == kSmNest0 || SMC == kSmNest2) {
-        // with the LDS image: the lean classes (leaf objects, classes 0-3 but DiffuseMetal) at 4 waves (128 VGPRs, 44 B
-        // of scratch), then DiffuseMetal and the composites (class 4: the nested-object record) at 3 (C4-shaped frame
-        // 113.2 -> 111.8 ms, profiles/r5/ab/c4_split_r5h.jsonl)
-        if (split && shm) {
-            RS_SHADE_LAUNCH(false, true, 1, shm);
-            if (class_mask & 0x14u) {
-                if (class_mask & (1u << 4)) RS_SHADE_LAUNCH(true, true, 2, shm);
-                else RS_SHADE_LAUNCH(false, true, 2, shm);
-            }
-            return hipGetLastError();
-        }
-        if (class_mask & (1u << 4)) { if (shm) RS_SHADE_LAUNCH(true, true, 0, shm); else RS_SHADE_LAUNCH(true, false, 0, 0); }
-        else { if (shm) RS_SHADE_LAUNCH(false, true, 0, shm); else RS_SHADE_LAUNCH(false, false, 0, 0); }
-    } else if (split) {
-        // the lean classes (Lambertian, Metal, Dielectric) at 4 waves, then the heavy ones (DiffuseMetal, the
-        // generic switch) at 3: the merged kernel's registers are DiffuseMetal's (168), Lambertian's alone 133
-        RS_SHADE_LAUNCH(false, false, 1, 0);
-        if (class_mask & 0x14u) {
-            if (class_mask & (1u << 4)) RS_SHADE_LAUNCH(true, false, 2, 0);
-            else RS_SHADE_LAUNCH(false, false, 2, 0);
-        }
+    const bool g4 = (class_mask & (1u << 4)) != 0;
+    auto launch = [&](auto g4_c, auto lobj, auto ps) {
+        hipLaunchKernelGGL((k_wfs_shade_all<SMC, decltype(g4_c)::value, decltype(lobj)::value, decltype(ps)::value>),
+                           dim3(blocks), dim3(kBlock), decltype(lobj)::value ? shm : 0, st, s.dev, w, queues, class_mask, it,
+                           depth, rad);
+    };
+    // Split: the lean classes (Lambertian, Metal, Dielectric; nest modes: leaf objects, classes 0-3 but DiffuseMetal)
+    // at 4 waves, then the heavy ones (DiffuseMetal, the generic switch; the composites' nested-object record, class
+    // 4) at 3: the merged kernel's registers are DiffuseMetal's (168), Lambertian's alone 133. The nest modes split
+    // only with the LDS image (128 VGPRs, 44 B of scratch; C4-shaped frame 113.2 -> 111.8 ms,
+    // profiles/r5/ab/c4_split_r5h.jsonl).
+    if (split && (!nest_mode(SMC) || shm)) {
+        using L = std::bool_constant<nest_mode(SMC)>;
+        launch(std::false_type{}, L{}, std::integral_constant<int, 1>{});
+        if (class_mask & 0x14u)
+            with_bool<true>(g4, [&](auto g4_c) { launch(g4_c, L{}, std::integral_constant<int, 2>{}); });
     } else {
-        if (class_mask & (1u << 4)) RS_SHADE_LAUNCH(true, false, 0, 0);
-        else RS_SHADE_LAUNCH(false, false, 0, 0);
+        with_bool<true>(g4, [&](auto g4_c) {
+            with_bool<nest_mode(SMC)>(shm != 0, [&](auto lobj) { launch(g4_c, lobj, std::integral_constant<int, 0>{}); });
+        });
     }
-#undef RS_SHADE_LAUNCH
     return hipGetLastError();
 }
 #endif  // RS_TU_MODES
@@ -2443,8 +2394,6 @@ RS_SORTED_LAUNCHERS(RS_INSTANTIATE_SM)
 #endif
 
 #if RS_TU_COMMON
-#define RS_DISPATCH_ALL(R, NAME, PARAMS, ARGS) \
-    R launch_##NAME PARAMS_SM_##NAME { RS_SM_DISPATCH(sm, return NAME##_sm<SMC> ARGS); return hipErrorInvalidValue; }
 hipError_t launch_probe_sample(const SceneRef& s, const DCamera& c, const PathParams& p, int sm, uint32_t x, uint32_t y,
                                uint32_t s0, uint32_t n, double* out, hipStream_t st) {
     RS_SM_DISPATCH(sm, return probe_sample_sm<SMC>(s, c, p, x, y, s0, n, out, st));
@@ -2547,23 +2496,8 @@ hipError_t launch_finalize(const double* acc, float* out_rgba, const FinalParams
 
 }  // namespace rs
 
-#if defined(RS_TRAV_STATS)
-#if !defined(RS_TU)
-#define RS_TS_FN rs_debug_trav_stats
-#elif RS_TU < 0
-#define RS_TS_FN rs_debug_trav_stats_c
-#elif RS_TU == 0
-#define RS_TS_FN rs_debug_trav_stats_0
-#elif RS_TU == 1
-#define RS_TS_FN rs_debug_trav_stats_1
-#elif RS_TU == 2
-#define RS_TS_FN rs_debug_trav_stats_2
-#elif RS_TU == 3
-#define RS_TS_FN rs_debug_trav_stats_3
-#else
-#define RS_TS_FN rs_debug_trav_stats_4
-#endif
-extern "C" int RS_TS_FN(unsigned long long out[128], int reset) {
+#ifdef RS_TRAV_STATS  // this unit's counters: rs_debug_trav_stats, _c, _0 .. _4
+extern "C" int RS_PASTE(rs_debug_trav_stats, RS_TU_SUFFIX)(unsigned long long out[128], int reset) {
     if (hipMemcpyFromSymbol(out, HIP_SYMBOL(rs::g_trav_stats), 128 * sizeof(unsigned long long)) != hipSuccess) return -3;
     if (reset) {
         unsigned long long z[128] = {0};

@@ -591,6 +591,45 @@ def test_deep_spheres_stack_spill_matches_oracle(gpu):
     assert np.array_equal(img, ref)
 
 
+def _leaf_row_scene(w=32, h=20):
+    """Twelve leaf objects (boxes, which make the scene reference-order, and spheres off the axis) in a row along
+    the view axis, growing with distance, and a sphere light above: the central rays reach every object's box,
+    the outer ones only the far boxes."""
+    from raysnail_amd.api import (Box, CameraBuilder, DiffuseLight, Gradient, HittableList, Lambertian, Metal,
+                                  Sphere, World)
+    from raysnail_amd.scenes import C32
+    hl, lights = HittableList(), HittableList()
+    for i in range(12):
+        z = -1.5 * i
+        mat = Lambertian(C32(0.2 + 0.06 * i, 0.7 - 0.04 * i, 0.5)) if i % 2 else Metal(C32(0.8, 0.8, 0.7))
+        if i % 3 == 2:
+            hl.add(Sphere((0.15 * ((i % 4) - 1.5), 0.1 * (i % 3), z), 0.45 + 0.02 * i, mat))
+        else:
+            hl.add(Box((-0.4 - 0.03 * i, -0.4, z - 0.3), (0.4 + 0.03 * i, 0.4 + 0.02 * i, z + 0.3), mat))
+    lamp = Sphere((0.0, 6.0, -8.0), 2.0, DiffuseLight(C32(1.0, 0.9, 0.8)).multiplier(4.0))
+    lights.add(lamp)
+    hl.add(lamp)
+    world = World(hl, lights, Gradient(C32(0.3, 0.4, 0.5), C32(0.7, 0.89, 1.0)), (0.0, 0.0))
+    cam = CameraBuilder().look_from((0.05, 0.1, 6.0)).look_at((0.0, 0.0, -8.0)).fov(20.0).width(w).height(h).build()
+    return cam, world
+
+
+def test_deferred_walk_second_window_matches_oracle(gpu):
+    """A nest-0 reference-order scene with its LDS image whose central rays reach more than kLeafBatch (8) leaf
+    boxes: the deferred walk (rs_kernels.hip traverse_deferred) lists its leaves in two windows, walking the tree
+    again for the second. The frame equals the oracle's bit for bit."""
+    cam, world = _leaf_row_scene()
+    info = world.device_scene().info()
+    assert info.scene_mode == 3  # nest-0
+    assert info.ref_order == 1 and info.tree_arity == 4
+    assert info.stack_need + 8 <= info.stack_lds  # the condition for the scene's LDS image (build_limg)
+    photo = cam.take_photo().samples(4).depth(4).seed(5).mode(A.RS_MODE_WAVEFRONT)
+    img = photo.shot(None, world)
+    ref, rs = _oracle(world).render(cam.desc, photo.settings())
+    assert photo.last_stats.segments == rs.segments
+    assert np.array_equal(img, ref)
+
+
 @pytest.mark.parametrize("name", ["rtow", "example_sdl", "quadric_sdl", "mesh"])
 def test_render_device_passes_stream(gpu, name):
     """rs_render_device_passes: n progressive passes of one frame (raysnail.rs:379-427's pass loop) as one sample
