@@ -294,6 +294,16 @@ private:
     MaterialRef mat_;
 };
 
+// src/hittable/geometry/raymarching.rs: the Mandelbulb about the origin (no parameters upstream). It renders
+// through libraysnail_hip only (rs_raymarcher); exporting it into another sink table throws RS_E_UNSUPPORTED.
+class RayMarcher : public Hittable {
+public:
+    explicit RayMarcher(MaterialRef mat) : mat_(std::move(mat)) {}
+    std::vector<uint32_t> export_to(SceneSink& sink) const override;
+private:
+    MaterialRef mat_;
+};
+
 class TriangleMesh : public Hittable {  // src/hittable/geometry/triangle_mesh.rs (one Triangle per face)
 public:
     // positions: 9 doubles per triangle; normals: 9 per triangle or empty (zero normals)

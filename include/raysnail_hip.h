@@ -25,6 +25,7 @@
  *   rs_box                   Box::new                         src/hittable/geometry/box.rs:40-45
  *   rs_quadric               Quadric::new                     src/hittable/geometry/quadric.rs:46-61
  *   rs_triangles             Triangle::new + set_normals      src/hittable/geometry/triangle_mesh.rs:42-71
+ *   rs_raymarcher            RayMarcher::new (Mandelbulb)     src/hittable/geometry/raymarching.rs:33-38
  *   rs_intersection          Intersection::new                src/hittable/csg/intersection.rs:33-39
  *   rs_difference            Difference::new                  src/hittable/csg/difference.rs:32-38
  *   rs_transformed           TfFacade::new + TransformStack   src/hittable/transform/tf_facade.rs:30-37,
@@ -247,6 +248,11 @@ int rs_aarect(rs_scene* s, int32_t plane, double k, double a0, double a1, double
 int rs_box(rs_scene* s, const double p0[3], const double p1[3], int32_t material, uint32_t* handle_out);
 int rs_quadric(rs_scene* s, const double q[10] /* qa qb qc qd qe qf qg qh qi qj */, int32_t material,
                uint32_t* handle_out);
+/* RayMarcher::new(material): the Mandelbulb distance-estimator object about the origin (bbox +-1.3, 100 iterations,
+   power 8: raymarching.rs has no parameters). Its hit() ignores the range end, so a world holding one is walked in
+   the reference's BVH order; the object exists in the generic scene mode (rs_scene_info::scene_mode 0) only.
+   An additive extension of ABI 6: no struct and no existing call changes, RS_ABI_VERSION stays 6. */
+int rs_raymarcher(rs_scene* s, int32_t material, uint32_t* handle_out);
 /* n triangles; pos = n*9 doubles (p0 p1 p2); nrm = n*9 doubles (n0 n1 n2) or NULL (zero normals,
  * Triangle::new default); handles are first_out .. first_out+n-1 */
 int rs_triangles(rs_scene* s, const double* pos, const double* nrm, uint32_t n, int32_t material,

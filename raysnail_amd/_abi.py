@@ -161,6 +161,8 @@ def load() -> C.CDLL:
     for name, (res, args) in SCENE_SIGNATURES.items():
         f = getattr(lib, "rs_" + name)
         f.restype, f.argtypes = res, args
+    # (not in SCENE_SIGNATURES: the test oracle has no RayMarcher)
+    lib.rs_raymarcher.restype, lib.rs_raymarcher.argtypes = C.c_int, [VP, C.c_int32, U32P]
     lib.rs_abi_version.restype = C.c_int
     lib.rs_last_error.restype = C.c_char_p
     lib.rs_device_count.argtypes = [C.POINTER(C.c_int)]
@@ -209,7 +211,7 @@ def load() -> C.CDLL:
 # every symbol include/raysnail_hip.h declares (checked by tests/test_abi.py)
 EXPORTED_SYMBOLS = [
     "rs_abi_version", "rs_last_error", "rs_device_count", "rs_stream_key", "rs_medium_uniform", "rs_scene_create",
-    "rs_scene_destroy", "rs_perlin", "rs_image", "rs_material", "rs_sphere", "rs_aarect", "rs_box", "rs_quadric", "rs_triangles", "rs_intersection",
+    "rs_scene_destroy", "rs_perlin", "rs_image", "rs_material", "rs_sphere", "rs_aarect", "rs_box", "rs_quadric", "rs_raymarcher", "rs_triangles", "rs_intersection",
     "rs_difference", "rs_transformed", "rs_constant_medium", "rs_world_add", "rs_lights_add", "rs_set_background", "rs_set_time_range",
     "rs_scene_commit", "rs_scene_commit_devices", "rs_scene_get_info", "rs_scene_set_lanes",
     "rs_scene_set_frames_in_flight", "rs_scene_set_workspace", "rs_render", "rs_render_rows", "rs_render_device", "rs_render_device_passes", "rs_combine_pixels_device", "rs_noise_map_device", "rs_noise_map",

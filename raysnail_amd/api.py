@@ -254,6 +254,11 @@ class Quadric(Hittable):             # src/hittable/geometry/quadric.rs (field o
         self.material = material
 
 
+class RayMarcher(Hittable):          # src/hittable/geometry/raymarching.rs (the Mandelbulb; no parameters)
+    def __init__(self, material: Optional[Material]):
+        self.material = material
+
+
 class TriangleMesh(Hittable):        # src/hittable/geometry/triangle_mesh.rs (Triangle list)
     def __init__(self, positions: np.ndarray, normals: Optional[np.ndarray], material: Optional[Material]):
         self.positions = np.ascontiguousarray(positions, dtype=np.float64).reshape(-1, 9)
@@ -460,6 +465,10 @@ def realize(world: World, lib, handle, prefix: str = "rs_") -> None:
             call("box", A.D3(*o.p0), A.D3(*o.p1), mat_id(o.material), C.byref(out))
         elif isinstance(o, Quadric):
             call("quadric", (C.c_double * 10)(*o.q), mat_id(o.material), C.byref(out))
+        elif isinstance(o, RayMarcher):
+            if prefix == "orc_":
+                raise RaysnailError(A.RS_E_UNSUPPORTED, "the test oracle has no RayMarcher")
+            call("raymarcher", mat_id(o.material), C.byref(out))
         elif isinstance(o, TriangleMesh):
             pos = o.positions
             nrm = o.normals

@@ -9,6 +9,7 @@
 // The per-primitive / per-material functions cite their reference lines below.
 #pragma once
 #include "../../include/rs_crmath.h"
+#include "rs_raymarch.h"
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "rs_layout.h"
@@ -400,9 +401,45 @@ __device__ __forceinline__ void tf_inverse_ray(const DScene& S, const DXform& X,
     }
 }
 
+// ------------------------------------------------------------------ RayMarcher ----
+// raymarching.rs through rs_raymarch.h (the arithmetic, shared with host code). Only Obj<L, 2> has the object:
+// the rich scene mode's kernels compiled once more for the scenes that hold a marcher (rs_internal.h kSmMarch),
+// so no other kernel -- the plain rich mode's included -- carries the march or is sized for its registers.
+// Each query is ONE out-of-line function: the object switch grows by a call per query, not by the march
+// (see composite_t's code-size note).
+__device__ __forceinline__ rs_rm::P3 rm_p3(V3 a) { return rs_rm::P3{a.x, a.y, a.z}; }
+// hit (:108-160) as (t1, t2, point): t1 = t2, point = ray.at(t1). The range end is not read (:141).
+__device__ RS_RM_CALL bool raymarch_hit_t(const Ray& r, double tmin, double& t1, V3& p) {
+    if (!rs_rm::hit_t(rm_p3(r.o), rm_p3(r.d), tmin, &t1)) return false;
+    p = ray_at(r, t1);
+    return true;
+}
+// normal (:78-91)
+__device__ RS_RM_CALL V3 raymarch_normal(V3 p) {
+    const rs_rm::P3 n = rs_rm::normal(rm_p3(p));
+    return v3(n.x, n.y, n.z);
+}
+// contains (:162-165)
+__device__ RS_RM_CALL bool raymarch_contains(V3 p) { return rs_rm::is_inside(rm_p3(p), rs_rm::kIterations); }
+// hit's record, HitRecord::new (hit.rs:32-53); uv (:97-106) is the sphere formula about the origin
+__device__ RS_RM_CALL bool raymarch_hit(int32_t mat, const Ray& r, double tmin, Hit& h, int uv) {
+    double t1;
+    V3 p;
+    if (!raymarch_hit_t(r, tmin, t1, p)) return false;
+    finish_rec(h, r, t1, t1, raymarch_normal(p), mat);
+    if (uv) {
+        DSphere about_origin;
+        about_origin.c[0] = about_origin.c[1] = about_origin.c[2] = 0.0;
+        sphere_uv(about_origin, h.p, h.u, h.v);
+    }
+    return true;
+}
+__device__ __forceinline__ V3 random_unit(Rng& rng);  // below; RayMarcher::random (:183-185)
+
 // ------------------------------------------------------------------ objects (nested) ----
 // Obj<L, R>: nested-object dispatch L levels deep; R = 1 in the rich scene mode (ConstantMedium,
-// records with (u, v)), 0 elsewhere, so the common kernels carry none of that code.
+// records with (u, v)), 2 in its variant with the RayMarcher kind, 0 elsewhere, so the common kernels carry
+// none of that code.
 template <int L, int R> struct Obj;
 
 // What the traversal and the CSG decisions read of a hit() record: t1, t2 and the point (a TfFacade
@@ -473,6 +510,13 @@ template <int L, int R> struct Obj {
             h.t1 = f.t1; h.t2 = f.t2; h.p = f.p;
             return true;
         }
+        case PK_RAYMARCH:  // raymarching.rs:108-160 (R = 2 only)
+            if constexpr (R != 2) return false;
+            else {
+                if (!raymarch_hit_t(r, tmin, h.t1, h.p)) return false;
+                h.t2 = h.t1;
+                return true;
+            }
         }
         return false;
     }
@@ -743,6 +787,9 @@ template <int L, int R> struct Obj {
             h.mat = M.mat; h.t1 = th; h.t2 = th; h.u = 0.0; h.v = 0.0; h.outside = 0;
             return true;
         }
+        case PK_RAYMARCH:  // raymarching.rs:108-160 (R = 2 only)
+            if constexpr (R != 2) return false;
+            else return raymarch_hit(P.mat, r, tmin, h, S.uv);
         }
         return false;
     }
@@ -802,6 +849,9 @@ template <int L, int R> struct Obj {
             }
             return false;
         }
+        case PK_RAYMARCH:  // is_inside(p, 100) (raymarching.rs:162-165; R = 2 only)
+            if constexpr (R != 2) return false;
+            else return raymarch_contains(p);
         default: return false;  // AARect / Triangle: false; ConstantMedium: unimplemented! upstream (constant.rs:86-91)
         }
     }
@@ -826,6 +876,9 @@ template <int L, int R> struct Obj {
             const DXform X = S.xforms[P.idx];
             return Obj<L - 1, R>::random(S, X.child, tf_inverse(S, X, P.aux, origin, 1.0), rng);
         }
+        case PK_RAYMARCH:  // Vec3::random_unit (raymarching.rs:183-185; R = 2 only)
+            if constexpr (R != 2) return v3(1.0, 0.0, 0.0);
+            else return random_unit(rng);
         default: return v3(1.0, 0.0, 0.0);  // Box / BVH / ConstantMedium (constant.rs:97-99)
         }
     }
@@ -836,6 +889,9 @@ template <int L, int R> struct Obj {
         case PK_SPHERE: return sphere_normal(S.spheres[P.idx], p);
         case PK_RECT: { int a = S.rects[P.idx].ax2; return v3(a == 0, a == 1, a == 2); }
         case PK_QUADRIC: return quadric_normal(S.quadrics[P.idx], p);
+        case PK_RAYMARCH:  // raymarching.rs:78-91 (R = 2 only)
+            if constexpr (R != 2) return v3(0.0, 1.0, 0.0);
+            else return raymarch_normal(p);
         default: return v3(0.0, 1.0, 0.0);  // Box::normal (box.rs:114-116)
         }
     }

@@ -375,6 +375,9 @@ struct rs_scene {
         }
         case PK_SUB: return bbox_t((uint32_t)o.a, time0, time1);
         case PK_MEDIUM: return bbox_t((uint32_t)o.a, time0, time1);  // constant.rs:93-95
+        case PK_RAYMARCH:  // raymarching.rs:167-176: center -/+ (1.3, 1.3, 1.3), center the origin
+            for (int i = 0; i < 3; ++i) { r.lo[i] = 0.0 - 1.3; r.hi[i] = 0.0 + 1.3; }
+            return r;
         case PK_XFORM: {
             Box3 b = bbox_t((uint32_t)o.a, time0, time1);
             std::vector<std::vector<double>> fwd;
@@ -402,7 +405,9 @@ struct rs_scene {
         const HObj& o = objs[h];
         if (o.kind == PK_SPHERE || o.kind == PK_RECT || o.kind == PK_TRIANGLE) return true;
         if (o.kind == PK_XFORM) return monotone((uint32_t)o.a);
-        return false;  // Box (outside/t2 depend on the far face), Quadric (a < 0 root order), CSG
+        // Box (outside/t2 depend on the far face), Quadric (a < 0 root order), CSG, RayMarcher (its hit() never
+        // reads the range end, raymarching.rs:141: a later marcher hit replaces a nearer earlier one)
+        return false;
     }
 
     int nest_depth(uint32_t h) const {
@@ -410,7 +415,7 @@ struct rs_scene {
         if (o.kind == PK_AND || o.kind == PK_SUB)
             return 1 + std::max(nest_depth((uint32_t)o.a), nest_depth((uint32_t)o.b));
         if (o.kind == PK_XFORM || o.kind == PK_MEDIUM) return 1 + nest_depth((uint32_t)o.a);
-        return 0;
+        return 0;  // leaves, RayMarcher among them
     }
 };
 
@@ -870,7 +875,7 @@ void build(rs_scene* s) {
             needs_lights = true;
     for (uint32_t h : s->world) {
         const HObj& o = s->objs[h];
-        if (o.mat == RS_NO_MATERIAL && o.kind <= PK_TRIANGLE) needs_lights = true;
+        if (o.mat == RS_NO_MATERIAL && (o.kind <= PK_TRIANGLE || o.kind == PK_RAYMARCH)) needs_lights = true;
     }
     if (needs_lights && s->lights.empty())
         throw Error(RS_E_NO_LIGHTS, "scene has pdf materials but an empty lights list (reference: % 0 panic, list.rs:51)");
@@ -933,6 +938,7 @@ void build(rs_scene* s) {
             DMedium x; x.boundary = o.a; x.mat = o.mat; x.neg_inv_density = o.p[0];
             P.idx = (int32_t)media.size(); media.push_back(x); break;
         }
+        case PK_RAYMARCH: P.idx = 0; break;  // no parameters (raymarching.rs:33-38)
         default: throw Error(RS_E_INVALID, "unknown object kind");
         }
     }
@@ -962,15 +968,17 @@ void build(rs_scene* s) {
     int nest = 0;
     for (uint32_t h : s->world) nest = std::max(nest, s->nest_depth(h));
     for (uint32_t h : s->lights) nest = std::max(nest, s->nest_depth(h));
-    // the rich features (ConstantMedium, Isotropic / BlinnPhong, Perlin / Image textures) exist only in
-    // the generic mode
+    // the rich features (ConstantMedium, RayMarcher, Isotropic / BlinnPhong, Perlin / Image textures) exist
+    // only in the generic mode
     bool rich = false;
-    for (const HObj& o : s->objs) rich = rich || o.kind == PK_MEDIUM;
+    for (const HObj& o : s->objs) rich = rich || o.kind == PK_MEDIUM || o.kind == PK_RAYMARCH;
     for (const rs_material_desc& d : s->mdesc)
         rich = rich || d.texture.kind == RS_TEX_PERLIN || d.texture.kind == RS_TEX_IMAGE || d.kind == RS_MAT_ISOTROPIC ||
                d.kind == RS_MAT_BLINN_PHONG;
     if (rich) s->spheres_only = false;
-    s->scene_mode = rich ? kSmGeneric : s->spheres_only ? kSmSpheres : flat ? kSmFlat : nest == 0 ? kSmNest0 : nest <= 2 ? kSmNest2 : kSmGeneric;
+    bool marcher = false;  // the generic mode's kernels with the RayMarcher kind (rs_internal.h kSmMarch)
+    for (const HObj& o : s->objs) marcher = marcher || o.kind == PK_RAYMARCH;
+    s->scene_mode = marcher ? kSmMarch : rich ? kSmGeneric : s->spheres_only ? kSmSpheres : flat ? kSmFlat : nest == 0 ? kSmNest0 : nest <= 2 ? kSmNest2 : kSmGeneric;
     bool all_monotone = true;
     for (uint32_t h : s->world) all_monotone = all_monotone && s->monotone(h);
     s->ref_order = !all_monotone;
@@ -1154,7 +1162,7 @@ void build(rs_scene* s) {
 #define RS_GENERIC_4W_MIN 0xFFFFFFFFu
 #endif
     const bool inorder4 = s->scene_mode == kSmNest0 || s->scene_mode == kSmNest2 ||
-                          (s->scene_mode == kSmGeneric && s->world.size() >= (size_t)RS_GENERIC_4W_MIN);
+                          (generic_mode(s->scene_mode) && s->world.size() >= (size_t)RS_GENERIC_4W_MIN);
     if (s->ref_order && inorder4 && root >= 0) {
         std::vector<HNode4> n4;
         int depth4 = 0;
@@ -2771,6 +2779,14 @@ int rs_quadric(rs_scene* s, const double q[10], int32_t mat, uint32_t* out) {
         *out = s->add(o);
     });
 }
+int rs_raymarcher(rs_scene* s, int32_t mat, uint32_t* out) {
+    return run([&] {
+        S(s)->check_mat(mat);
+        if (!out) throw Error(RS_E_INVALID, "null argument");
+        HObj o; o.kind = PK_RAYMARCH; o.mat = mat;  // RayMarcher::new (raymarching.rs:33-38): iterations = 100
+        *out = s->add(o);
+    });
+}
 int rs_triangles(rs_scene* s, const double* pos, const double* nrm, uint32_t n, int32_t mat, uint32_t* first) {
     return run([&] {
         S(s)->check_mat(mat);
@@ -2877,7 +2893,7 @@ int rs_scene_get_info(const rs_scene* s, rs_scene_info* out) {
         std::memset(out, 0, sizeof(*out));
         out->tree_arity = s->tree_arity;
         out->ref_order = s->ref_order ? 1 : 0;
-        out->scene_mode = s->scene_mode;
+        out->scene_mode = generic_mode(s->scene_mode) ? (int)kSmGeneric : s->scene_mode;  // kSmMarch: the generic mode + one kind
         out->tree_depth = s->tree_depth;
         out->stack_need = s->stack_need;
         out->stack_lds = stack_lds(s->scene_mode);
@@ -2976,7 +2992,7 @@ int rs_probe_world_hit(rs_scene* s, const double* rays, uint32_t n, double tmin,
         HIP_OK(hipMalloc((void**)&dout, (size_t)n * 13 * sizeof(double) + 8));
         HIP_OK(hipMemcpy(dr, rays, (size_t)n * 7 * sizeof(double), hipMemcpyHostToDevice));
         ensure_stack_overflow(s, R, ((uint64_t)n + kBlock - 1) / kBlock * kBlock);
-        HIP_OK(launch_probe_hit(R.ref(), dr, n, tmin, tmax, dout, nullptr));
+        HIP_OK(launch_probe_hit(R.ref(), dr, n, tmin, tmax, dout, s->scene_mode, nullptr));
         HIP_OK(hipMemcpy(out, dout, (size_t)n * 13 * sizeof(double), hipMemcpyDeviceToHost));
         (void)hipFree(dr);
         (void)hipFree(dout);

@@ -24,12 +24,18 @@ constexpr uint32_t kMaxSlots = 4;   // frames in flight per replica (rs_scene_se
 // triangles only (no CSG / transforms / boxes / quadrics: leaf tests without the nested object
 // machinery); kSmNest0 / kSmNest2 -- anything with at most 0 / 2 levels of CSG / TfFacade nesting
 // (the nested-object code is instantiated only as deep as the scene needs: fewer registers, no
-// scratch); kSmGeneric -- up to RS_MAX_NEST levels.
-enum SceneMode { kSmGeneric = 0, kSmSpheres = 1, kSmFlat = 2, kSmNest0 = 3, kSmNest2 = 4 };
-constexpr int nest_of(int sm) { return sm == kSmNest0 ? 0 : sm == kSmNest2 ? 2 : sm == kSmGeneric ? RS_MAX_NEST : 0; }
+// scratch); kSmGeneric -- up to RS_MAX_NEST levels; kSmMarch -- the generic mode's kernels compiled once more
+// with the RayMarcher kind (rs_device.h PK_RAYMARCH) for the scenes that hold one. A kernel is given the
+// registers of the hungriest function it can call: with the marcher's out-of-line functions in the generic
+// unit itself every rich scene's kernels fell from 2 waves per SIMD to 1 (k_wf_extend<0>: 242 -> 256 VGPRs,
+// scratch 1120 -> 1928 B), marcher or not. rs_scene_info reports both as scene mode 0.
+enum SceneMode { kSmGeneric = 0, kSmSpheres = 1, kSmFlat = 2, kSmNest0 = 3, kSmNest2 = 4, kSmMarch = 5 };
+constexpr bool generic_mode(int sm) { return sm == kSmGeneric || sm == kSmMarch; }
+constexpr int march_of(int sm) { return sm == kSmMarch ? 1 : 0; }
+constexpr int nest_of(int sm) { return sm == kSmNest0 ? 0 : sm == kSmNest2 ? 2 : generic_mode(sm) ? RS_MAX_NEST : 0; }
 // the generic mode is also the rich one: ConstantMedium, Perlin / Image textures, (u, v) records
 // (commit puts every scene that uses them there; the other modes compile none of that code)
-constexpr int rich_of(int sm) { return sm == kSmGeneric ? 1 : 0; }
+constexpr int rich_of(int sm) { return generic_mode(sm) ? 1 : 0; }
 // the streaming (material-sorted) wavefront serves these modes; flat (mesh) and generic scenes run
 // the bounce-synchronous unsorted wavefront
 constexpr bool streaming_mode(int sm) { return sm == kSmSpheres || sm == kSmNest0 || sm == kSmNest2; }
@@ -38,7 +44,7 @@ constexpr bool streaming_mode(int sm) { return sm == kSmSpheres || sm == kSmNest
 // 5 blocks per CU resident; at 16 entries the C5 mesh frame is 10 % faster although more of its deep entries
 // spill to HBM, C4 2.5 % and example.sdl 1.6 %; the rich mode (X2) lost 4 % (profiles/r4/ab/lds_stack). The
 // spheres mode takes 16 since round 5: its extend's LDS tree top (kLTop) then fits 5 blocks per CU.
-constexpr int stack_lds(int sm) { return sm == kSmGeneric ? kStackMax : kStackMin; }
+constexpr int stack_lds(int sm) { return generic_mode(sm) ? kStackMax : kStackMin; }
 // the nest modes' LDS scene image (rs_layout.h kLimgMax) next to their stack: four 256-thread blocks per CU
 // must fit the CU's 160 KiB of LDS
 static_assert(4u * ((uint32_t)stack_lds(kSmNest0) * kBlock * 4u + kLimgMax) <= 160u * 1024u, "LDS image budget");
@@ -205,7 +211,7 @@ hipError_t wf_occupancy(int sm, int* extend_blocks_per_cu, int* shade_blocks_per
 hipError_t launch_combine(float* acc, const float* nw, uint64_t n, float p, hipStream_t st);
 hipError_t launch_noise(const float* px, int w, int h, float t, uint8_t* redo, unsigned int* minmax_bits,
                         unsigned long long* count, hipStream_t st);
-hipError_t launch_probe_hit(const SceneRef& s, const double* rays, uint32_t n, double tmin, double tmax, double* out,
+hipError_t launch_probe_hit(const SceneRef& s, const double* rays, uint32_t n, double tmin, double tmax, double* out, int sm,
                             hipStream_t st);
 // acc[c * n_pix + pixel] += sum over the batch's samples in sample order (deterministic; item-major
 // radiance rad[3 * item + c], items sample-plane by sample-plane); the last batch writes into_color of the sum into the frame instead (k_finalize's

@@ -58,6 +58,7 @@
         case kSmFlat: { constexpr int SMC = kSmFlat; __VA_ARGS__; break; }       \
         case kSmNest0: { constexpr int SMC = kSmNest0; __VA_ARGS__; break; }     \
         case kSmNest2: { constexpr int SMC = kSmNest2; __VA_ARGS__; break; }     \
+        case kSmMarch: { constexpr int SMC = kSmMarch; __VA_ARGS__; break; }     \
         default: { constexpr int SMC = kSmGeneric; __VA_ARGS__; break; }         \
         }                                                                  \
     } while (0)
@@ -373,15 +374,15 @@ __device__ __forceinline__ void test_sphere_leaf(const DScene& S, const DSphere&
 // Nested-object entry points: Obj<L> instantiated only as deep as the scene mode needs.
 template <int SM>
 __device__ __forceinline__ bool obj_hit(const DScene& S, int p, const Ray& r, double tmin, double tmax, Hit& h) {
-    return Obj<nest_of(SM), rich_of(SM)>::hit(S, p, r, tmin, tmax, h);
+    return Obj<nest_of(SM), rich_of(SM) + march_of(SM)>::hit(S, p, r, tmin, tmax, h);
 }
 template <int SM>
 __device__ __forceinline__ bool obj_hit_t(const DScene& S, int p, const Ray& r, double tmin, double tmax, HitT& h) {
-    return Obj<nest_of(SM), rich_of(SM)>::hit_t(S, p, r, tmin, tmax, h);
+    return Obj<nest_of(SM), rich_of(SM) + march_of(SM)>::hit_t(S, p, r, tmin, tmax, h);
 }
 template <int SM>
 __device__ __forceinline__ V3 obj_random(const DScene& S, int p, V3 origin, Rng& rng) {
-    return Obj<nest_of(SM), rich_of(SM)>::random(S, p, origin, rng);
+    return Obj<nest_of(SM), rich_of(SM) + march_of(SM)>::random(S, p, origin, rng);
 }
 
 // Object hit for flat scenes (spheres, rects, triangles; no nesting): Obj<L>::hit's leaf cases only.
@@ -829,7 +830,7 @@ __device__ __forceinline__ int traverse(const DScene& S, const Ray& r, double tm
     TravStat st;
     // (the generic mode carries it too: its kernels include the World::hit probe, k_probe_hit, which
     // serves every scene mode's trees)
-    if ((SM == kSmNest0 || SM == kSmNest2 || SM == kSmGeneric) && S.root4 >= 0 && S.ref_order) {
+    if ((SM == kSmNest0 || SM == kSmNest2 || generic_mode(SM)) && S.root4 >= 0 && S.ref_order) {
         // BVH::hit's recursion order on the in-order 4-wide tree, each leaf tested when its box is reached: the
         // boxes after it see the range it left behind
         walk4_inorder<LOBJ, false>(S, rf, tmin32, best32, stk, st, [&](int c) RS_INLINE_LAMBDA {
@@ -2171,9 +2172,11 @@ __global__ __launch_bounds__(kBlock) void k_noise(const float4* __restrict__ px,
 }
 #endif  // RS_TU_COMMON
 
-#if RS_TU_COMMON
+#if RS_TU_COMMON || RS_TU == 5
 // Diagnostic: World::hit for a batch of rays (tests/ per-primitive parity probes).
 // rays[i] = o(3) d(3) time; out[i] = hit t1 t2 p(3) n(3) 0 0 outside mat  (13 doubles, oracle layout)
+// SM: kSmGeneric (the common unit: it serves every scene mode's trees) or kSmMarch (that mode's unit)
+template <int SM>
 __global__ __launch_bounds__(kBlock) void k_probe_hit(const DScene* __restrict__ Sp, const double* __restrict__ rays, uint32_t n, double tmin,
                                                      double tmax, double* __restrict__ out) {
     const DScene& S = *Sp;  // the scene lives in device memory: no by-value copy in scratch
@@ -2188,14 +2191,24 @@ __global__ __launch_bounds__(kBlock) void k_probe_hit(const DScene* __restrict__
     for (int k = 0; k < 13; ++k) o[k] = 0.0;
     // range end handled by clamping best: world_hit starts from +inf, so emulate [tmin, tmax) by a
     // post-check only when tmax is infinite (the render path always passes +inf)
-    if (world_hit<kSmGeneric>(S, r, tmin, h, make_stk(S, stk_all)) && h.t1 < tmax) {
+    if (world_hit<SM>(S, r, tmin, h, make_stk(S, stk_all)) && h.t1 < tmax) {
         o[0] = 1.0; o[1] = h.t1; o[2] = h.t2;
         o[3] = h.p.x; o[4] = h.p.y; o[5] = h.p.z; o[6] = h.n.x; o[7] = h.n.y; o[8] = h.n.z;
         if (S.uv) { o[9] = h.u; o[10] = h.v; }  // (u, v) exist only in scenes that read them
         o[11] = h.outside ? 1.0 : 0.0; o[12] = (double)h.mat;
     }
 }
-#endif  // RS_TU_COMMON
+// the marcher variant's probe, launched from its own unit
+hipError_t probe_hit_march(const SceneRef& s, const double* rays, uint32_t n, double tmin, double tmax, double* out,
+                           uint32_t blocks, hipStream_t st);
+#if !defined(RS_TU) || RS_TU == 5
+hipError_t probe_hit_march(const SceneRef& s, const double* rays, uint32_t n, double tmin, double tmax, double* out,
+                           uint32_t blocks, hipStream_t st) {
+    hipLaunchKernelGGL(k_probe_hit<kSmMarch>, dim3(blocks), dim3(kBlock), 0, st, s.dev, rays, n, tmin, tmax, out);
+    return hipGetLastError();
+}
+#endif
+#endif  // RS_TU_COMMON or the marcher unit
 
 // Diagnostic: the radiance and world.hit count of samples s0 .. s0+n-1 of pixel (x, y), each
 // through the megakernel's trace_path (tests/ per-sample parity; the oracle's orc_sample_radiance).
@@ -2469,10 +2482,11 @@ hipError_t launch_noise(const float* px, int w, int h, float t, uint8_t* redo, u
 }
 
 hipError_t launch_probe_hit(const SceneRef& s, const double* rays, uint32_t n, double tmin, double tmax, double* out,
-                            hipStream_t st) {
+                            int sm, hipStream_t st) {
     const uint32_t blocks = (n + kBlock - 1) / kBlock;
     if (!blocks) return hipSuccess;
-    hipLaunchKernelGGL(k_probe_hit, dim3(blocks), dim3(kBlock), 0, st, s.dev, rays, n, tmin, tmax, out);
+    if (sm == kSmMarch) return probe_hit_march(s, rays, n, tmin, tmax, out, blocks, st);
+    hipLaunchKernelGGL(k_probe_hit<kSmGeneric>, dim3(blocks), dim3(kBlock), 0, st, s.dev, rays, n, tmin, tmax, out);
     return hipGetLastError();
 }
 
@@ -2496,7 +2510,7 @@ hipError_t launch_finalize(const double* acc, float* out_rgba, const FinalParams
 
 }  // namespace rs
 
-#ifdef RS_TRAV_STATS  // this unit's counters: rs_debug_trav_stats, _c, _0 .. _4
+#ifdef RS_TRAV_STATS  // this unit's counters: rs_debug_trav_stats, _c, _0 .. _5
 extern "C" int RS_PASTE(rs_debug_trav_stats, RS_TU_SUFFIX)(unsigned long long out[128], int reset) {
     if (hipMemcpyFromSymbol(out, HIP_SYMBOL(rs::g_trav_stats), 128 * sizeof(unsigned long long)) != hipSuccess) return -3;
     if (reset) {

@@ -20,6 +20,7 @@ enum PrimKind : int32_t {
     PK_SUB = 6,     // csg Difference    (src/hittable/csg/difference.rs)
     PK_XFORM = 7,   // TfFacade          (src/hittable/transform/tf_facade.rs)
     PK_MEDIUM = 8,  // ConstantMedium    (src/hittable/medium/constant.rs)
+    PK_RAYMARCH = 9,  // RayMarcher      (src/hittable/geometry/raymarching.rs; no per-object data: idx 0)
 };
 
 // One entry per hittable handle (world objects and nested children alike).

@@ -198,6 +198,15 @@ std::vector<uint32_t> Box::export_to(SceneSink& sink) const {
     return {h};
 }
 
+// rs_raymarcher is not a slot of the sink table (the table's layout is shared with sinks that have no marcher,
+// such as the tests' CPU oracle): it is called directly when the sink is libraysnail_hip's own table.
+std::vector<uint32_t> RayMarcher::export_to(SceneSink& sink) const {
+    if (&sink.api != &hip_sink_api()) throw Error(RS_E_UNSUPPORTED, "this scene sink has no RayMarcher");
+    uint32_t h = 0;
+    sink.check(rs_raymarcher(static_cast<rs_scene*>(sink.scene), sink.material(mat_), &h));
+    return {h};
+}
+
 std::vector<uint32_t> Quadric::export_to(SceneSink& sink) const {
     uint32_t h = 0;
     sink.check(sink.api.quadric(sink.scene, q_.data(), sink.material(mat_), &h));

@@ -25,10 +25,10 @@ import numpy as np
 
 import os
 
-from .api import (AARect, AARectMetrics, BVH, BlinnPhong, Box, CameraBuilder, Checker, Color, ConstantMedium,
-                  Dielectric, Difference, DiffuseLight, DiffuseMetal, Glass, Gradient, HittableList, Image,
-                  Intersection, Lambertian, Metal, Perlin, Point3, Quadric, SmoothType, Sphere, TfFacade,
-                  Transform, TransformStack, TriangleMesh, World)
+from .api import (AARect, AARectMetrics, BVH, BlinnPhong, Box, CameraBuilder, Checker, Color, CommonMaterialSettings,
+                  ConstantMedium, Dielectric, Difference, DiffuseLight, DiffuseMetal, Glass, Gradient, HittableList,
+                  Image, Intersection, Lambertian, Metal, Perlin, Point3, Quadric, RayMarcher, SmoothType, Sphere,
+                  TfFacade, Transform, TransformStack, TriangleMesh, World)
 
 M32 = 0xFFFFFFFF
 M64 = 0xFFFFFFFFFFFFFFFF
@@ -274,6 +274,24 @@ def example_sdl(width: int = 800, height: int = 500):
     h.add(Sphere((0.0, -10002.0, 0.0), 10000.0, Lambertian(C32(0.07, 0.06, 0.05))))
     world = _cli_world(h, [((300.0, 400.0, 100.0), C32(1.0, 0.9, 0.7))], cam)
     return cam, world
+
+
+def raymarching_test(width: int = 800, height: int = 500):
+    """examples/preview_sdl2.rs:338-406 (render_raymarching_test): the Mandelbulb over a checker ground.
+    Returns (camera, world, samples=122, depth=8)."""
+    look_from = Point3(13.0 * 0.7, -1.7 * 0.7, 3.0 * 0.7)  # Point3::new(13.0, -1.7, 3.0) * 0.7
+    cam = CameraBuilder().look_from(look_from).look_at(Point3(0.0, -0.4, 0.0)).fov(20.0).aperture(0.01).focus(10.0) \
+        .width(width).height(height).build()
+    h, lights = HittableList(), HittableList()
+    rs = Sphere((300.0, 400.0, 100.0), 12.0, DiffuseLight(C32(1.0, 0.9, 0.8)).multiplier(1.5))
+    lights.add(rs)
+    h.add(rs)
+    material = Lambertian(C32(0.5, 0.5, 0.5)).set(CommonMaterialSettings(phong_factor=4.0, phong_exponent=2))
+    h.add(RayMarcher(material))
+    h.add(Sphere((0.0, -1002.0, 0.0), 1000.0,
+                 DiffuseMetal(800.0, Checker(C32(0.26, 0.3, 0.16), C32(0.1, 0.1, 0.1), 10.0))))
+    world = World(h, lights, Gradient(C32(0.68, 0.80, 0.95), C32(0.2, 0.4, 0.7)), (0.0, cam.shutter_speed))
+    return cam, world, 122, 8
 
 
 def _translated(obj, t):

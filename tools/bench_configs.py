@@ -33,6 +33,9 @@ def configs():
                lambda: scenes.all_feature_scene(800, 800), 64, 50),
         "X2": ("cornell_smoke (two ConstantMedium boxes), 600x600, 64 spp, depth 50",
                lambda: scenes.cornell_smoke(600, 600), 64, 50),
+        # the RayMarcher preview scene (examples/preview_sdl2.rs:338-406). No CPU baseline: the oracle has no marcher
+        "X3": ("raymarching_test (Mandelbulb RayMarcher over a checker ground), 800x500, 122 -> 121 spp, depth 8",
+               lambda: scenes.raymarching_test(800, 500)[:2], 122, 8, False),
     }
 
 
@@ -61,9 +64,10 @@ def main():
     torch.cuda.set_device(0)
     from oracle.binding import OracleScene
     only = set(filter(None, args.only.split(",")))
-    for key, (desc, build, spp, depth) in configs().items():
+    for key, (desc, build, spp, depth, *opt) in configs().items():
         if only and key not in only:
             continue
+        has_oracle = not opt or opt[0]
         cam, world = build()
         t0 = time.perf_counter()
         ds = world.device_scene()
@@ -96,22 +100,27 @@ def main():
         dt = sorted(times)[len(times) // 2]
         assert np.array_equal(frame.cpu().numpy(), img, equal_nan=True), "device frame differs from the host frame"
         gpu_msps = st.samples / dt / 1e6
-        # CPU oracle: rows 0::k with k chosen from a probe so the run takes ~cpu_seconds
-        orc = OracleScene(world)
-        probe_rows = max(1, H // 64)
-        ps = photo.rows(0, 0, H // probe_rows).settings()
-        t0 = time.perf_counter()
-        _, pst = orc.render(cam.desc, ps, threads=args.cpu_threads)
-        tp = time.perf_counter() - t0
-        per_sample = tp / max(1, pst.samples)
-        want = args.cpu_seconds / per_sample
-        k = max(1, int(round(st.samples / max(1.0, want))))
-        cs = photo.rows(0, 0, k).settings()
-        t0 = time.perf_counter()
-        ref, cst = orc.render(cam.desc, cs, threads=args.cpu_threads)
-        tc = time.perf_counter() - t0
-        cpu_msps = cst.samples / tc / 1e6
-        same_rows = bool((img[::k] == ref[::k]).all())
+        cpu, speedup, same_rows = None, None, None
+        if has_oracle:
+            # CPU oracle: rows 0::k with k chosen from a probe so the run takes ~cpu_seconds
+            orc = OracleScene(world)
+            probe_rows = max(1, H // 64)
+            ps = photo.rows(0, 0, H // probe_rows).settings()
+            t0 = time.perf_counter()
+            _, pst = orc.render(cam.desc, ps, threads=args.cpu_threads)
+            tp = time.perf_counter() - t0
+            per_sample = tp / max(1, pst.samples)
+            want = args.cpu_seconds / per_sample
+            k = max(1, int(round(st.samples / max(1.0, want))))
+            cs = photo.rows(0, 0, k).settings()
+            t0 = time.perf_counter()
+            ref, cst = orc.render(cam.desc, cs, threads=args.cpu_threads)
+            tc = time.perf_counter() - t0
+            cpu_msps = cst.samples / tc / 1e6
+            same_rows = bool((img[::k] == ref[::k]).all())
+            cpu = {"Msamples_per_s": round(cpu_msps, 4), "threads": args.cpu_threads, "kind": "port",
+                   "sample": f"rows 0::{k} ({cst.samples} samples) in {tc:.1f} s"}
+            speedup = round(gpu_msps / cpu_msps, 1)
         # roofline (bench.py's fields): the dominant kernel's launches event-timed in the host-output frame above
         # (its extends -- and the streaming finish, which traces the frame's last segments -- or the bounce-synchronous
         # extends), SURVEY 8(d)'s 44 B per segment; and the frame model 212 B/segment + 124 B/sample over the
@@ -135,9 +144,7 @@ def main():
                                        "segments_per_sample": round(st.segments / st.samples, 4),
                                        "launches": st.launches, "commit_s": round(t_commit, 3)},
                "roofline": roof,
-               "cpu_baseline": {"Msamples_per_s": round(cpu_msps, 4), "threads": args.cpu_threads, "kind": "port",
-                                "sample": f"rows 0::{k} ({cst.samples} samples) in {tc:.1f} s"},
-               "speedup": round(gpu_msps / cpu_msps, 1), "sampled_rows_bit_identical": same_rows}
+               "cpu_baseline": cpu, "speedup": speedup, "sampled_rows_bit_identical": same_rows}
         print(json.dumps(out), flush=True)
 
 
