@@ -299,7 +299,9 @@ int rs_scene_set_frames_in_flight(rs_scene* s, uint32_t frames);
  * -- camera samples injected per iteration times the iterations a path can span; capped per device so
  * that the pools of its frame slots and lanes take at most two thirds of its memory, and, when a frame
  * slot allocates its pool, by the memory then free on the device (other allocations of the process
- * shrink the pool instead of failing the render; RS_E_NOMEM only when not even a 256-path pool fits)
+ * shrink the pool instead of failing the render; RS_E_NOMEM only when not even the floor fits: the
+ * frame's pool or 64 Ki x max(depth, 1) paths, whichever is smaller, for the streaming wavefront, a
+ * chunk of the frame's size or 1 Mi paths, whichever is smaller, for the bounce-synchronous one)
  * -- and the chunk of the bounce-synchronous wavefront). pool_paths is a soft bound: an iteration injects at least 256
  * samples (one block), so a pool below 256 x depth paths is raised to that for the frame.
  * Scheduling only: frames are bitwise the same for any value. */

@@ -1356,33 +1356,33 @@ uint64_t splitmix64_h(uint64_t x) {
     return z ^ (z >> 31);
 }
 
-// grow a device buffer; `owner` (a slot or a replica) is quiesced first: frames in flight may still
-// use the old one
-template <typename T, class Q>
-void ensure(Q& owner, T*& p, size_t& cap, size_t n) {
-    if (n <= cap) return;
-    if (p) { owner.quiesce(); HIP_OK(hipFree(p)); }
-    p = nullptr;
-    cap = 0;
-    HIP_OK(hipMalloc((void**)&p, n * sizeof(T)));
-    cap = n;
+// hipMalloc that reports an out-of-memory device as false (*p null then) instead of throwing
+bool try_malloc(void** p, size_t bytes) {
+    const hipError_t e = hipMalloc(p, bytes);
+    if (e == hipErrorOutOfMemory) {
+        (void)hipGetLastError();  // not sticky: clear it for the next call's checks
+        *p = nullptr;
+        return false;
+    }
+    HIP_OK(e);
+    return true;
 }
-// ensure() that reports an out-of-memory device as false (nothing held then) instead of throwing
+// grow a device buffer; `owner` (a slot or a replica) is quiesced first: frames in flight may still
+// use the old one. False, with nothing held, when the device is out of memory.
 template <typename T, class Q>
 bool try_ensure(Q& owner, T*& p, size_t& cap, size_t n) {
     if (n <= cap) return true;
     if (p) { owner.quiesce(); HIP_OK(hipFree(p)); }
     p = nullptr;
     cap = 0;
-    const hipError_t e = hipMalloc((void**)&p, n * sizeof(T));
-    if (e == hipErrorOutOfMemory) {
-        (void)hipGetLastError();
-        p = nullptr;
-        return false;
-    }
-    HIP_OK(e);
+    if (!try_malloc((void**)&p, n * sizeof(T))) return false;
     cap = n;
     return true;
+}
+// try_ensure() that throws when the device is out of memory
+template <typename T, class Q>
+void ensure(Q& owner, T*& p, size_t& cap, size_t n) {
+    if (!try_ensure(owner, p, cap, n)) throw Error(RS_E_HIP, std::string("hipMalloc failed: ") + hipGetErrorString(hipErrorOutOfMemory));
 }
 
 // Traversal-stack overflow for launches of at most `threads` grid threads: (stack_need - kStackMax)
@@ -1422,13 +1422,7 @@ bool carve_wf(Slot& L, uint64_t cap, uint32_t lanes) {
         L.wf_cap = 0;
         L.wf_lanes = 0;
         L.wf_bytes = 0;
-        const hipError_t e = hipMalloc(&L.d_wf, lane_bytes * lanes);
-        if (e == hipErrorOutOfMemory) {
-            (void)hipGetLastError();  // not sticky: clear it for the next call's checks
-            L.d_wf = nullptr;
-            return false;
-        }
-        HIP_OK(e);
+        if (!try_malloc(&L.d_wf, lane_bytes * lanes)) return false;
         L.wf_cap = c;
         L.wf_lanes = lanes;
         L.wf_bytes = lane_bytes * lanes;
@@ -1466,6 +1460,18 @@ struct DeviceGuard {
     }
     ~DeviceGuard() { if (prev >= 0) (void)hipSetDevice(prev); }
 };
+// Owners of what a render call creates for itself (move-only). An entry point drains the devices before these
+// go out of scope on an error: what it enqueued may still use them.
+template <class T, hipError_t (*Free)(T*)>
+struct HipFree { void operator()(T* p) const { (void)Free(p); } };
+using Event = std::unique_ptr<ihipEvent_t, HipFree<ihipEvent_t, hipEventDestroy>>;
+using DeviceMem = std::unique_ptr<void, HipFree<void, hipFree>>;
+using PinnedMem = std::unique_ptr<void, HipFree<void, hipHostFree>>;
+// record an untimed event, created when first recorded
+void record(Event& e, hipStream_t st) {
+    if (!e) { hipEvent_t h; HIP_OK(hipEventCreateWithFlags(&h, hipEventDisableTiming)); e.reset(h); }
+    HIP_OK(hipEventRecord(e.get(), st));
+}
 
 // Rows of the call's lattice (row_begin, row_end, row_step) that replica k of n renders: every n-th
 // lattice row starting at the k-th, the interleave of render_rows (painter.rs:248) over devices.
@@ -1516,11 +1522,12 @@ struct FrameSched {
     uint64_t n_counts = 0;              // counter words of all lanes
     uint64_t cap = 0;                   // pool records per set (the largest lane's)
 };
-// The enqueue order of a frame (render_enqueue walks it; make_sched dry-runs it to size the ring):
+// The enqueue order of a frame (enqueue_streaming walks it; make_sched dry-runs it to size the ring):
 // iterations round robin over the lanes; after each, every accumulate whose batches are complete, in
-// batch order. visit(l, t) for an iteration, acc(k) for an accumulate.
-template <class FI, class FA>
-void walk(const FrameSched& f, FI visit, FA acc) {
+// batch order. visit(l, t) for an iteration, fin(l, k) for each batch k of lane l that was complete with it, acc(k)
+// for an accumulate.
+template <class FI, class FD, class FA>
+void walk(const FrameSched& f, FI visit, FD fin, FA acc) {
     std::vector<uint64_t> t(f.lanes, 0), m_done(f.lanes, 0);
     std::vector<char> done(f.n_batches, 0);
     uint32_t next_acc = 0;
@@ -1531,7 +1538,10 @@ void walk(const FrameSched& f, FI visit, FA acc) {
             if (t[l] >= L.T) continue;
             any = true;
             visit(l, t[l]);
-            while (m_done[l] < L.batch.size() && L.done_it(m_done[l]) == t[l]) done[L.batch[m_done[l]++]] = 1;
+            while (m_done[l] < L.batch.size() && L.done_it(m_done[l]) == t[l]) {
+                fin(l, L.batch[m_done[l]]);
+                done[L.batch[m_done[l]++]] = 1;
+            }
             ++t[l];
             while (next_acc < f.n_batches && done[next_acc]) acc(next_acc++);
         }
@@ -1597,7 +1607,7 @@ FrameSched make_sched(const rs_scene* s, uint64_t n_pix, uint32_t N, uint32_t D,
                  if (L.first_it(m) == t && start[L.batch[m]] == UINT64_MAX) start[L.batch[m]] = step;
              ++step;
          },
-         [&](uint32_t k) { acc_at[k] = step; });
+         [](uint32_t, uint32_t) {}, [&](uint32_t k) { acc_at[k] = step; });
     for (uint32_t k = 0; k < f.n_batches; ++k) {
         uint32_t live = 1;
         // per lane its batches start in order: count each lane's later batches begun before acc(k)
@@ -1614,17 +1624,19 @@ FrameSched make_sched(const rs_scene* s, uint64_t n_pix, uint32_t N, uint32_t D,
 
 // One replica's share of a frame between enqueue and finish: multi-device renders enqueue every
 // replica before waiting for any, so the devices run concurrently.
+enum class Scheme { Mega, Batched, Streaming };  // megakernel, bounce-synchronous wavefront, streaming wavefront
 struct Pending {
     Replica* R = nullptr;
     Slot* L = nullptr;
     uint32_t rec_bytes = 104;       // a path record as the kernels write it (96: the tag in ray_o.w, tag_in_ray)
     hipStream_t stream = nullptr;   // the stream the frame ends on (the caller's, or the replica's own)
     bool empty = true;
-    int kind = 0;                   // 0 megakernel, 1 bounce-synchronous wavefront, 2 streaming wavefront
+    Scheme kind = Scheme::Mega;
     bool timed = false;             // per-kernel events; the frame runs alone
     bool counted = false;           // the queue counters are kept for render_finish (statistics)
-    uint32_t n_pix = 0, N = 0, depth = 0, n_batches = 0, path_launches = 0, n_frames = 1;
+    uint32_t n_pix = 0, N = 0, depth = 0, path_launches = 0, n_frames = 1;
     uint64_t n_chunks_total = 0;
+    size_t n_counts = 0;            // queue counter words of the frame (none: megakernel, no samples)
     std::vector<LaneSched> lanes;               // streaming: the lanes' schedules
     std::vector<std::vector<uint32_t>> inj;     // streaming: camera samples injected per lane and iteration
     size_t ki = 0;
@@ -1637,11 +1649,18 @@ struct Pending {
     }
 };
 
+// Frame slots a replica cycles through (render_enqueue takes slot next_slot % frame_slots): one for trees
+// whose traversal stack spills to the replica's shared HBM overflow array, else frames_in_flight. Callers
+// that keep several frames (bands) in flight must not exceed it: two frames in one slot share its counters.
+uint32_t frame_slots(const rs_scene* s) {
+    if (s->stack_need > stack_lds(s->scene_mode)) return 1u;
+    return std::max<uint32_t>(1, std::min(kMaxSlots, s->frames_in_flight));
+}
+
 // The pool (paths per lane and set) of a frame on slot L of replica R streaming on `lanes` lanes: the scene's bound,
 // capped so that the pools of all the replica's frame slots take at most two thirds of the device memory (kPathBytes
 // per path and lane; 288 GB holds three slots of 256 Mi paths on one lane). A pool size is scheduling only: frames do
 // not depend on it (rs_host.cpp make_sched, tests/test_gpu_parity.py test_streaming_pool_and_async_bit_identical).
-uint32_t frame_slots(const rs_scene* s);
 uint64_t pool_limit(const rs_scene* s, const Replica& R, uint32_t lanes) {
     const uint64_t per = kPathBytes * std::max<uint32_t>(1, lanes);
     return std::min<uint64_t>(s->pool_paths, std::max<uint64_t>(kBlock, R.mem_total / 3 * 2 / (frame_slots(s) * per)));
@@ -1682,24 +1701,13 @@ void release_pool(Slot& L) {
 #endif
 constexpr uint64_t kSplitShadeMin = RS_SPLIT_SHADE_MIN;
 
-// Frame slots a replica cycles through (render_enqueue takes slot next_slot % frame_slots): one for trees
-// whose traversal stack spills to the replica's shared HBM overflow array, else frames_in_flight. Callers
-// that keep several frames (bands) in flight must not exceed it: two frames in one slot share its counters.
-uint32_t frame_slots(const rs_scene* s) {
-    if (s->stack_need > stack_lds(s->scene_mode)) return 1u;
-    return std::max<uint32_t>(1, std::min(kMaxSlots, s->frames_in_flight));
-}
-
 void validate_render(const rs_scene* s, const rs_camera_desc* cam, const rs_render_settings* st) {
     if (!cam || !st) throw Error(RS_E_INVALID, "null argument");
     if (!s->committed) throw Error(RS_E_STATE, "scene not committed");
     if (s->reps.empty()) throw Error(RS_E_STATE, "scene committed without devices (host-only build)");
     if (cam->width == 0 || cam->height == 0) throw Error(RS_E_INVALID, "empty image");
     if (st->mode < RS_MODE_AUTO || st->mode > RS_MODE_WAVEFRONT) throw Error(RS_E_INVALID, "unknown render mode");
-    const uint32_t re = st->row_end ? std::min(st->row_end, cam->height) : cam->height;
-    const uint32_t rstep = st->row_step ? st->row_step : 1;
-    if (st->row_begin < re && (uint64_t)((re - st->row_begin + rstep - 1) / rstep) * cam->width > 0xFFFFFFFFull)
-        throw Error(RS_E_INVALID, "frame too large");
+    if ((uint64_t)replica_rows(cam, st, 0, 1).count() * cam->width > 0xFFFFFFFFull) throw Error(RS_E_INVALID, "frame too large");
 }
 
 hipStream_t lane_stream(Slot& L, uint32_t l) {
@@ -1731,6 +1739,497 @@ InjParams inj_params(const FrameSched& f, const LaneSched& ln, uint64_t t) {
     return I;
 }
 
+// What render_enqueue derives from a call before it picks a scheme: values only (the replica, the slot, the stream
+// the frame ends on and the frame's sizes are in Pending).
+struct FrameConsts {
+    DCamera dc; PathParams pp; FinalParams fp; SceneRef ds;
+    uint32_t spb = 0;                  // sample planes per radiance batch
+    bool ext_spill = false;            // the traversal stack spills to the replica's shared HBM overflow
+    uint32_t wide = 0, ext_cap = 0, ext_blocks = 0, shade_blocks = 0;  // launch grids (render_enqueue)
+    float* d_out = nullptr;
+    float* const* outs = nullptr;      // a multi-pass stream's frames; the ones before the last are written
+    hipEvent_t outs_after = nullptr;   // after this event
+};
+
+// `to` goes on after what `from` holds now
+void join(hipEvent_t ev, hipStream_t from, hipStream_t to) {
+    HIP_OK(hipEventRecord(ev, from));
+    HIP_OK(hipStreamWaitEvent(to, ev, 0));
+}
+// the frame's end on S: join L0 into S, then the last accumulate there (it writes the caller's frame)
+void join_to_end(Slot& L, hipStream_t S) {
+    if (S != L.lane[0]) join(L.join_ev[0], L.lane[0], S);
+}
+// fork: the slot's lane streams 1.. start after what L0 (lane 0) holds
+void fork_lanes(Slot& L, uint32_t lanes) {
+    if (!L.fork_ev) HIP_OK(hipEventCreateWithFlags(&L.fork_ev, hipEventDisableTiming));
+    HIP_OK(hipEventRecord(L.fork_ev, L.lane[0]));
+    for (uint32_t l = 1; l < lanes; ++l) HIP_OK(hipStreamWaitEvent(lane_stream(L, l), L.fork_ev, 0));
+}
+// join: `to` continues after every lane's work
+void join_lanes(Slot& L, uint32_t lanes, hipStream_t to) {
+    for (uint32_t l = 1; l < lanes; ++l) join(L.join_ev[l], L.lane[l], to);
+}
+// a timed frame's events (Pending destroys them)
+void new_events(std::vector<hipEvent_t>& ev, size_t n) {
+    ev.assign(n, nullptr);
+    for (auto& e : ev) HIP_OK(hipEventCreate(&e));
+}
+// The frame's queue counters: n_counts words of L.d_counts, zero when the frame's launches on L0 run (the leading
+// counts_clean words were reset by the last frame's accumulate).
+void prepare_counts(Slot& L, size_t n_counts, hipStream_t L0) {
+    uint32_t* const prev_counts = L.d_counts;
+    ensure(L, L.d_counts, L.counts_cap, n_counts);
+    if (L.d_counts != prev_counts) L.counts_clean = 0;
+    if (n_counts > L.counts_clean) HIP_OK(hipMemsetAsync(L.d_counts, 0, n_counts * sizeof(uint32_t), L0));
+    L.counts_clean = 0;
+}
+// the last batch's accumulate finishes the frame (into_color) and, when no statistics
+// read the queue counters afterwards, zeroes them for the next frame (no memset launch)
+void accumulate_last(const Pending& P, const double* rad, uint32_t planes, bool first, const FinalParams& fp, float* out) {
+    const size_t nz = P.counted ? 0 : P.n_counts;
+    HIP_OK(launch_accumulate(rad, P.L->d_acc, P.n_pix, planes, first, 1, fp, out, P.L->d_counts, (uint32_t)nz, P.stream));
+    P.L->counts_clean = nz;
+}
+
+// Pool negotiation. plan(pool) schedules the frame on at most `pool` paths per lane and set and says what that
+// needs of the slot; alloc(need) gets it (false: the device cannot, and the slot holds none of it). The pool is
+// pool_limit's; where the slot has to allocate, at most what the device has free; an allocation that still fails
+// (memory taken meanwhile) halves it, down to the floor: the first plan's paths, at most `floor`.
+struct PoolNeed { uint64_t cap; uint32_t lanes; size_t rad; };  // paths per lane and set, lanes, radiance ring (doubles)
+template <class Plan, class Alloc>
+void fit_pool(const rs_scene* s, const Replica& R, Slot& L, uint32_t want, uint64_t floor, Plan plan, Alloc alloc) {
+    uint64_t pool = pool_limit(s, R, want);
+    PoolNeed need = plan(pool);
+    const uint64_t pool_min = std::min<uint64_t>(need.cap, floor);
+    if (need.cap > L.wf_cap || need.lanes > L.wf_lanes || need.rad > L.rad_cap) {
+        // the slot allocates: as much as the device has free
+        const uint64_t fp = std::max(pool_min, pool_limit_free(s, R, L, want, need.rad * sizeof(double)));
+        if (fp < pool) need = plan(pool = fp);
+    }
+    while (!alloc(need)) {
+        if (pool <= pool_min) throw Error(RS_E_NOMEM, "device memory exhausted: no room for the frame's path pool");
+        need = plan(pool = std::max<uint64_t>(pool_min, pool / 2));
+    }
+}
+
+// no samples: into_color of 0 / 0 (NaN, or 0 with the mask) for every lattice pixel
+void enqueue_empty(const FrameConsts& c, Pending& P) {
+    Slot& L = *P.L;
+    HIP_OK(hipMemsetAsync(L.d_acc, 0, (size_t)3 * P.n_pix * sizeof(double), L.lane[0]));
+    join_to_end(L, P.stream);
+    HIP_OK(launch_finalize(L.d_acc, c.d_out, c.fp, P.stream));
+}
+
+// Carried-extend grids. Without history a carried launch takes a block per 256 of the paths injected in the
+// last depth - 1 iterations (the bound on what it can carry), though from the second bounce on it carries a
+// few of them (bench frame: 28 % at t = 2, 3 % at t = 7): the empty blocks only read the count and leave, but
+// their dispatch costs a launch some microseconds. A frame of the same shape as one completed earlier takes
+// that frame's count of the iteration + 25 % + 16 Ki paths (blocks grid-stride over what exceeds it, so the
+// frame never depends on the estimate). The counts reach pinned host memory at the end of each frame
+// (Slot::h_hist) and are read here without waiting (bench frame 6.47 -> 6.39 ms with a fixed cap,
+// profiles/r6/ab/carried_cap_r6g1.txt).
+struct GridHist {
+    uint64_t sig = 0;            // the frame's schedule signature
+    std::vector<size_t> hoff;    // per lane: its first word
+    size_t hwords = 0;           // per iteration: the paths carried in, the paths queued for shading
+    bool hint = false;           // Replica::hist holds a completed frame of this schedule
+};
+// the frame's history layout; takes over the counts of slots whose frames have completed (without waiting) and
+// makes room for this frame's
+GridHist hist_begin(Replica& R, Slot& L, const FrameSched& f, uint32_t n_pix, uint32_t N, uint32_t D, uint32_t n_frames) {
+    GridHist h;
+    h.sig = splitmix64_h(((uint64_t)n_pix << 32) ^ N) ^ splitmix64_h(((uint64_t)D << 40) ^ ((uint64_t)f.lanes << 32) ^ n_frames);
+    for (const LaneSched& ln : f.lane) {
+        h.sig = splitmix64_h(h.sig ^ ln.Q ^ (ln.T << 40) ^ (ln.total << 1) ^ (uint64_t)ln.finish);
+        h.hoff.push_back(h.hwords);
+        h.hwords += 2 * ln.T;
+    }
+    for (Slot& o : R.slots) {
+        if (!o.hist_pending) continue;
+        const hipError_t q = hipEventQuery(o.hist_ev);
+        if (q == hipSuccess) {
+            o.hist_pending = false;
+            R.hist.assign(o.h_hist, o.h_hist + o.hist_words);
+            R.hist_sig = o.hist_sig;
+        } else {
+            (void)hipGetLastError();  // hipErrorNotReady: not an error here
+            if (q != hipErrorNotReady) HIP_OK(q);
+        }
+    }
+#ifndef RS_NO_GRID_HINT  // (dev A/B: every carried launch over a block per 256 paths of the window)
+    h.hint = R.hist_sig == h.sig && R.hist.size() == h.hwords;
+#endif
+    if (L.hist_cap < h.hwords) {
+        if (L.h_hist) { HIP_OK(hipEventSynchronize(L.hist_ev)); HIP_OK(hipHostFree(L.h_hist)); L.h_hist = nullptr; }
+        HIP_OK(hipHostMalloc((void**)&L.h_hist, h.hwords * sizeof(uint32_t)));
+        L.hist_cap = h.hwords;
+        L.hist_pending = false;
+    }
+    if (!L.hist_ev) HIP_OK(hipEventCreateWithFlags(&L.hist_ev, hipEventDisableTiming));
+    return h;
+}
+// n_max paths capped by the earlier frame's count `word` (0 carried, 1 queued) of lane l's iteration t, + `more`
+uint64_t hist_grid(const GridHist& h, const Replica& R, uint32_t l, uint64_t t, int word, uint64_t n_max, uint64_t more = 0) {
+    if (!h.hint) return n_max;
+    const uint64_t est = R.hist[h.hoff[l] + 2 * t + word];
+    return std::min<uint64_t>(n_max, est + est / 4 + 64ull * kBlock + more);
+}
+// the frame's carried and queued counts (words 0 and 1 of each lane's iterations' counter blocks)
+// for later frames' grids, before the accumulate zeroes them
+void hist_end(const GridHist& h, Slot& L, const FrameSched& f, hipStream_t S) {
+    for (uint32_t l = 0; l < f.lanes; ++l)
+        HIP_OK(hipMemcpy2DAsync(L.h_hist + h.hoff[l], 2 * sizeof(uint32_t), L.d_counts + f.lane[l].cnt_off,
+                                kWfsStride * sizeof(uint32_t), 2 * sizeof(uint32_t), f.lane[l].T,
+                                hipMemcpyDeviceToHost, S));
+    HIP_OK(hipEventRecord(L.hist_ev, S));
+    L.hist_pending = true;
+    L.hist_sig = h.sig;
+    L.hist_words = h.hwords;
+}
+
+// A streaming frame being enqueued: what its iterations and accumulates share (enqueue_streaming).
+struct StreamFrame {
+    const rs_scene* s; const FrameConsts& c; Pending& P; Slot& L;
+    FrameSched f;
+    GridHist h;
+    bool split, split_shade;
+    // per lane: the samples injected by its last depth - 1 iterations (a bound on the paths it
+    // carries into the next one) (the injections per iteration: P.inj)
+    std::vector<uint64_t> window;
+    // per batch: its paths are done (recorded on its lane) / it has been accumulated (acc stream)
+    hipEvent_t done_ev(uint32_t k) const { return L.bev[2 * (size_t)k]; }
+    hipEvent_t acc_ev(uint32_t k) const { return L.bev[2 * (size_t)k + 1]; }
+    void iteration(uint32_t l, uint64_t t);
+    void accumulate(uint32_t k);
+};
+
+// iteration t of lane l (walk's visit)
+void StreamFrame::iteration(uint32_t l, uint64_t t) {
+    const bool timed = P.timed;
+    const uint32_t D = P.depth;
+    const int sm = s->scene_mode;
+    const LaneSched& ln = f.lane[l];
+    const hipStream_t cs = L.lane[l];
+    WfState WS = L.lane_ws[l];
+    WS.tagw = tag_in_ray(c.ds);
+    WS.counts = L.d_counts + ln.cnt_off;
+    QEnt** qd = L.d_qptrs[l];
+    const uint32_t n_new = ln.n_new(t);
+    P.inj[l][t] = n_new;
+    InjParams I = inj_params(f, ln, t);
+    if (n_new) {
+        const uint64_t m = t * ln.Q / f.B;
+        // a batch taking over a ring buffer: after the batch `ring` earlier was accumulated
+        for (uint64_t mm = m; mm <= m + 1 && mm < ln.batch.size(); ++mm) {
+            const uint32_t kk = ln.batch[mm];
+            if (ln.first_it(mm) == t && kk >= f.ring) HIP_OK(hipStreamWaitEvent(cs, acc_ev(kk - f.ring), 0));
+        }
+    }
+    if (ln.finish && t + 1 == ln.T) {  // the finish: every carried path to its end, one launch
+        const uint32_t b = (uint32_t)std::min<uint64_t>(c.wide, (window[l] + kBlock - 1) / kBlock);
+        // timed with the extends: it traces the World::hit of every segment it runs (the statistics
+        // count them on this iteration), so the dominant kernel's time covers the frame's segments
+        if (timed) HIP_OK(hipEventRecord(P.kev[2 * P.ki], cs));
+        HIP_OK(launch_wfs_finish(c.ds, WS, (uint32_t)t, D, L.d_rad, std::max<uint32_t>(1, b), sm, cs));
+        if (timed) HIP_OK(hipEventRecord(P.kev[2 * P.ki + 1], cs));
+        ++P.ki;
+        ++P.path_launches;
+        window[l] = 0;
+        return;
+    }
+    auto extend = [&](int part, uint64_t n_max) {
+        if (part == kExtCarried) n_max = hist_grid(h, *P.R, l, t, 0, n_max);
+        const uint32_t b = (uint32_t)std::min<uint64_t>(c.ext_cap, (n_max + kBlock - 1) / kBlock);
+        if (!b) return;
+        HIP_OK(launch_wfs_extend(c.ds, c.dc, c.pp, WS, qd, (uint32_t)t, I, L.d_rad, b, part, sm, cs,
+                                 timed ? P.kev[2 * P.ki] : nullptr, timed ? P.kev[2 * P.ki + 1] : nullptr));
+        ++P.ki;
+        ++P.path_launches;
+    };
+    // an iteration with only carried paths (or only camera samples) runs the kernel compiled for
+    // that part alone: nest-0 example.sdl 8.95 -> 8.41 ms; the spheres mode's carried part runs at 5
+    // waves (ext_min_waves), bench frame 7.58 -> 7.31 ms (profiles/r5/ab; at 4 waves its parts had
+    // measured 2.8 % slower than the merged kernel, profiles/r4/ab/part_pick)
+    if (split) {
+        extend(kExtCarried, window[l]);
+        extend(kExtCamera, n_new);
+    } else if (n_new == 0) {
+        extend(kExtCarried, window[l]);
+    } else if (window[l] == 0) {
+        extend(kExtCamera, n_new);
+    } else {
+        extend(kExtAll, window[l] + n_new);
+    }
+    if (D > 0) {
+        uint64_t n_sh = window[l] + n_new;  // the paths it may shade: at most the live ones
+#ifndef RS_NO_SHADE_HINT  // (dev A/B)
+        // the camera launch shades most of its hits itself: the grid from the earlier frame's
+        // queued count of the iteration (k_wfs_shade_all writes it next to the carried count)
+        n_sh = cam_fused(sm, kExtCamera) ? hist_grid(h, *P.R, l, t, 1, n_sh) : hist_grid(h, *P.R, l, t, 0, n_sh, n_new);
+#endif
+        const uint32_t b = (uint32_t)std::min<uint64_t>(c.wide, (n_sh + kBlock - 1) / kBlock);
+        HIP_OK(launch_wfs_shade_all(c.ds, WS, qd, s->class_mask, (uint32_t)t, D, L.d_rad, b, split_shade, sm, cs));
+        ++P.path_launches;
+    }
+    // carried into t + 1: the samples injected by iterations t - depth + 2 .. t
+    window[l] += n_new;
+    if (D == 0) window[l] = 0;
+    else if (t + 1 >= D) window[l] -= P.inj[l][t + 1 - D];
+}
+
+// batch k's samples have all finished: accumulate in sample order (the last batch on S,
+// writing the frame and zeroing the counters for the next frame unless statistics read them;
+// an earlier pass's last batch into its frame, on the accumulate stream) (walk's acc)
+void StreamFrame::accumulate(uint32_t k) {
+    const hipStream_t S = P.stream;
+    const uint32_t fr = k / f.nbpf, kl = k % f.nbpf;
+    float* const out = P.n_frames > 1 ? c.outs[fr] : c.d_out;
+    const uint32_t planes = (uint32_t)(std::min<uint64_t>(f.B, (uint64_t)P.n_pix * P.N - (uint64_t)kl * f.B) / P.n_pix);
+    const double* rk = L.d_rad + (size_t)3 * (k % f.ring) * f.B;  // item-major radiance (put_rad)
+    if (k + 1 < f.n_batches) {
+        HIP_OK(hipStreamWaitEvent(L.acc_stream, done_ev(k), 0));
+        HIP_OK(launch_accumulate(rk, L.d_acc, P.n_pix, planes, kl == 0, kl + 1 == f.nbpf ? 1 : 0, c.fp, out,
+                                 nullptr, 0, L.acc_stream));
+        HIP_OK(hipEventRecord(acc_ev(k), L.acc_stream));
+        return;
+    }
+    join(L.join_ev[0], L.acc_stream, S);
+    HIP_OK(hipStreamWaitEvent(S, done_ev(k), 0));
+    join_lanes(L, f.lanes, S);  // (every lane's last iteration, for the counters)
+    join(L.fork_ev, L.lane[0], S);
+    hist_end(h, L, f, S);
+    accumulate_last(P, rk, planes, kl == 0, c.fp, out);
+}
+
+// The streaming wavefront (streaming scene modes): the schedule on a pool that fits, the counters, the lanes and
+// the accumulate stream forked off L0, then the schedule's walk.
+void enqueue_streaming(const rs_scene* s, const rs_render_settings* st, const FrameConsts& c, Pending& P) {
+    Slot& L = *P.L;
+    const hipStream_t L0 = L.lane[0];
+    const uint32_t n_pix = P.n_pix, N = P.N, D = P.depth, n_frames = P.n_frames;
+    StreamFrame F{s, c, P, L};
+    FrameSched& f = F.f;
+    const uint32_t want = c.ext_spill ? 1u : std::min<uint32_t>(kMaxLanes, s->stream_lanes);
+    // the smallest pool a frame is scheduled on: 64 Ki camera samples per iteration (or the whole frame); below
+    // that the iterations (and their counter blocks) multiply, and the render reports the device as full
+    fit_pool(s, *P.R, L, want, (uint64_t)65536 * std::max<uint32_t>(D, 1),
+             [&](uint64_t pool) {
+                 f = make_sched(s, n_pix, N, D, want, pool, n_frames);
+                 return PoolNeed{f.cap, f.lanes, (size_t)3 * f.ring * f.B};
+             },
+             [&](const PoolNeed& need) {  // both buffers, or both back
+                 if (carve_wf(L, need.cap, need.lanes) && try_ensure(L, L.d_rad, L.rad_cap, need.rad)) return true;
+                 release_pool(L);
+                 return false;
+             });
+    f.keys.resize(n_frames);
+    for (uint32_t k = 0; k < n_frames; ++k)
+        f.keys[k] = splitmix64_h(splitmix64_h(st->seed) ^ (uint64_t)(st->pass + k));
+    prepare_counts(L, P.n_counts = f.n_counts, L0);
+    F.h = hist_begin(*P.R, L, f, n_pix, N, D, n_frames);
+    // every lane and the accumulate stream start after L0's dependencies and the counter reset
+    if (!L.acc_stream) HIP_OK(hipStreamCreateWithFlags(&L.acc_stream, hipStreamNonBlocking));
+    fork_lanes(L, f.lanes);
+    HIP_OK(hipStreamWaitEvent(L.acc_stream, L.fork_ev, 0));
+    if (n_frames > 1) HIP_OK(hipStreamWaitEvent(L.acc_stream, c.outs_after, 0));
+    while (L.bev.size() < 2 * (size_t)f.n_batches) {
+        hipEvent_t e;
+        HIP_OK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+        L.bev.push_back(e);
+    }
+    // (a multi-pass stream's iterations carry paths and inject camera samples: two launches, each part at its own
+    // occupancy -- 30 share frames of the bench frame 0.971 -> 0.909 ms, profiles/r6/passes)
+    F.split = ext_split(s->scene_mode) || s->ext_split || n_frames > 1;
+    // lean / heavy shading launches (spheres mode; nest modes with an LDS image) pay one more launch tail per
+    // iteration: worth it on full frames (bench 7.16 -> 7.09 ms), not on small ones (the N = 8 row share, 3.2 M
+    // samples: 1.013 -> 1.066 ms)
+    F.split_shade = s->shade_split && (uint64_t)n_pix * N >= kSplitShadeMin;
+    size_t n_ext = 0;
+    for (const LaneSched& ln : f.lane) n_ext += ln.T * (F.split ? 2 : 1);
+    new_events(P.kev, P.timed ? 2 * n_ext : 0);
+    new_events(P.ev, P.timed ? 2 : 0);  // path_ms: the frame's iterations
+    if (P.timed) HIP_OK(hipEventRecord(P.ev[0], L0));
+    P.lanes.assign(f.lane.begin(), f.lane.end());
+    F.window.assign(f.lanes, 0);
+    P.inj.resize(f.lanes);
+    for (uint32_t l = 0; l < f.lanes; ++l) P.inj[l].assign(f.lane[l].T, 0u);
+    walk(f, [&](uint32_t l, uint64_t t) { F.iteration(l, t); },
+         [&](uint32_t l, uint32_t k) { HIP_OK(hipEventRecord(F.done_ev(k), L.lane[l])); },  // once the lane gets here
+         [&](uint32_t k) { F.accumulate(k); });
+    if (P.timed) HIP_OK(hipEventRecord(P.ev[1], P.stream));
+}
+// A streaming frame's segments and bytes from its queue counters (render_finish).
+void count_streaming(const rs_scene* s, const Pending& P, rs_render_stats* stats) {
+    uint64_t seg = 0, kbytes = 0;
+    // the streaming extend's library byte model, per iteration: ray records in (64 B)
+    // per carried path; the queue entry with the hit (16 B) per queued segment; the record out (96 B + item
+    // + level) per live camera sample (written after its traversal for the ones that go on to the shading
+    // launch, or after its in-place shading for a lean-class hit of the spheres mode's camera launch, whose
+    // survivors write the level-1 record and the others 24 B of radiance: an upper bound); radiance out (24 B)
+    // per path ending in extend unshaded, + its throughput record and item in (36 B); radiance out for masked
+    // samples. `fused`: the camera hits shaded inside the extend (word 1 of the statistics lines): they are
+    // neither queued nor ended there
+    for (size_t l = 0; l < P.lanes.size(); ++l)
+        for (uint64_t t = 0; t < P.lanes[l].T; ++t) {
+            const uint32_t* q = &P.qc[P.lanes[l].cnt_off + t * kWfsStride];
+            uint64_t live_new = 0, shaded = 0, fused = 0;
+            for (uint32_t k = 0; k < kStatLines; ++k) live_new += q[cix(kCntStat0 + (int)k)];
+            for (uint32_t k = 0; k < kStatLines; ++k) fused += q[cix(kCntStat0 + (int)k) + 1];
+            for (int k = 0; k < kWfsClasses; ++k) shaded += q[cix(1 + k)];
+            const uint64_t old = q[cix(0)], live = old + live_new;
+            if (P.lanes[l].finish && t + 1 == P.lanes[l].T) {
+                // the finish: its carried paths' first segments and (stat lines) the ones after; a record in
+                // (104 B) and a radiance out (24 B) per path
+                seg += live;
+                kbytes += 128ull * old;
+                continue;
+            }
+            const uint64_t dead_new = P.inj[l][t] - live_new;
+            const uint64_t ended = live - shaded - fused;
+            seg += live;
+            kbytes += 64ull * old + 16ull * shaded + (uint64_t)P.rec_bytes * live_new + 60ull * ended + 24ull * dead_new;
+#ifdef RS_DEV_KNOBS
+            if (s->dump_iters) {
+                const uint32_t* qn = q + kWfsStride;  // the next set's runs
+                std::fprintf(stderr, "iter lane %zu t %3llu: carried %9llu (front %9u back %9u) camera %9llu shaded %9llu"
+                             " [%u %u %u %u %u] fused %9llu ended %9llu -> next front %9u back %9u\n", l, (unsigned long long)t,
+                             (unsigned long long)old, q[cix(kCntFront)], q[cix(kCntBack)], (unsigned long long)live_new,
+                             (unsigned long long)shaded, q[cix(1)], q[cix(2)], q[cix(3)], q[cix(4)], q[cix(5)],
+                             (unsigned long long)fused, (unsigned long long)ended, qn[cix(kCntFront)], qn[cix(kCntBack)]);
+            }
+#endif
+        }
+    stats->kernel_id = RS_KERNEL_WFS_EXTEND;
+    stats->kernel_bytes += kbytes;
+    stats->segments += seg;
+}
+
+// bounce-synchronous wavefront (flat / rich scenes) or megakernel: per batch of spb sample planes
+void enqueue_batched(const rs_scene* s, const rs_render_settings* st, const FrameConsts& c, Pending& P) {
+    Slot& L = *P.L;
+    const hipStream_t L0 = L.lane[0];
+    const uint32_t n_pix = P.n_pix, N = P.N, D = P.depth, spb = c.spb;
+    const bool wavefront = st->mode != RS_MODE_MEGAKERNEL, timed = P.timed;
+    const int sm = s->scene_mode;
+    PathParams pp = c.pp;
+    ensure(L, L.d_rad, L.rad_cap, (size_t)3 * n_pix * spb);
+    // Wavefront lanes (rs_scene_set_lanes, default 2): a batch's chunks go round-robin to lane streams
+    // and run concurrently, so one lane's launch tails and small late-bounce launches overlap the
+    // other's work. Chunks are whole sample planes when the batch allows (camera-ray tile order,
+    // gen_perm). Scenes whose traversal stack spills to HBM keep one lane (the overflow array is
+    // shared by blockIdx).
+    const uint32_t want = (wavefront && !c.ext_spill) ? std::min<uint32_t>(kMaxLanes, s->wf_lanes) : 1u;
+    uint32_t lanes = want;
+    uint64_t chunk = 0;
+    auto plan = [&](uint64_t pool) {  // chunks of at most `pool` paths per lane
+        lanes = want;
+        chunk = std::max<uint64_t>(kBlock, std::min<uint64_t>(pool, (uint64_t)n_pix * spb));
+        if (lanes > 1) {
+            const uint64_t planes = (spb + lanes - 1) / lanes;
+            const uint64_t split = std::max<uint64_t>(kBlock, spb >= lanes ? (uint64_t)n_pix * planes
+                                                                           : ((uint64_t)n_pix * spb + lanes - 1) / lanes);
+            chunk = std::min(chunk, split);
+        }
+        P.n_chunks_total = 0;
+        for (uint32_t s0 = 0; s0 < N; s0 += spb) P.n_chunks_total += ((uint64_t)n_pix * std::min(spb, N - s0) + chunk - 1) / chunk;
+        if (P.n_chunks_total < lanes) lanes = std::max<uint32_t>(1, (uint32_t)P.n_chunks_total);
+        return PoolNeed{chunk, lanes, L.rad_cap};  // (the slot's radiance buffer, allocated above, stays)
+    };
+    if (wavefront) {
+        // chunks of at least 1 Mi paths
+        fit_pool(s, *P.R, L, want, 1ull << 20, plan, [&](const PoolNeed& need) { return carve_wf(L, need.cap, need.lanes); });
+        P.n_counts = (size_t)P.n_chunks_total * (D + 1);
+    } else {
+        plan(pool_limit(s, *P.R, want));
+    }
+    const size_t n_batches = (N + spb - 1) / spb;
+    new_events(P.ev, timed ? 2 * n_batches : 0);
+    new_events(P.kev, timed ? 2 * (wavefront ? (size_t)P.n_chunks_total * D : n_batches) : 0);
+    if (!wavefront || timed) HIP_OK(hipMemsetAsync(L.d_cnt, 0, 512 * sizeof(unsigned long long), L0));
+    prepare_counts(L, P.n_counts, L0);
+    uint32_t bi = 0;
+    uint64_t chunk_i = 0;
+    for (uint32_t s0 = 0; s0 < N; s0 += spb, ++bi) {
+        const uint32_t nb = std::min(spb, N - s0);
+        pp.s0 = s0;
+        pp.n_items = (uint64_t)n_pix * nb;
+        if (timed) HIP_OK(hipEventRecord(P.ev[2 * bi], L0));
+        if (!wavefront) {
+            if (timed) HIP_OK(hipEventRecord(P.kev[2 * P.ki], L0));
+            HIP_OK(launch_path_mega(c.ds, c.dc, pp, sm, L.d_rad, L.d_cnt, c.wide, L0));
+            if (timed) HIP_OK(hipEventRecord(P.kev[2 * P.ki + 1], L0));
+            ++P.ki;
+            ++P.path_launches;
+        } else {
+            if (lanes > 1) fork_lanes(L, lanes);
+            uint32_t lane = 0;
+            for (uint64_t c0 = 0; c0 < pp.n_items; c0 += chunk, ++chunk_i, lane = (lane + 1) % lanes) {
+                const uint32_t n = (uint32_t)std::min<uint64_t>(chunk, pp.n_items - c0);
+                WfState WS = L.lane_ws[lane];
+                WS.tagw = tag_in_ray(c.ds);
+                WS.counts = L.d_counts + chunk_i * (D + 1);
+                const hipStream_t cs = L.lane[lane];
+                // a pixel mask: k_wf_gen compacts the live samples into set 0's shards (counts from zero)
+                if (pp.mask) HIP_OK(hipMemsetAsync(WS.heads, 0, 8 * 32 * sizeof(uint32_t), cs));
+                HIP_OK(launch_wf_gen(c.dc, pp, WS, c0, n, L.d_rad, cs));
+                ++P.path_launches;
+                for (uint32_t b = 0; b < D; ++b) {
+                    if (timed) HIP_OK(hipEventRecord(P.kev[2 * P.ki], cs));
+                    // meshes: one block per 256 paths (C5 49.6 -> 48.1 ms), at most 64 per CU where the tree
+                    // spills its stack to HBM (the overflow array is sized for that grid; a grid of resident
+                    // blocks only, grid-striding, made the C5 extend 35 % slower); the rich mode a bounded grid
+                    const uint32_t bn = (n + kBlock - 1) / kBlock;
+                    // flat scenes on the 4-wide tree: the persistent extend (k_wf_extend_dyn), one resident grid
+                    const uint32_t eb = sm == kSmFlat ? (flat_dyn(c.ds) ? std::min(c.ext_blocks, bn)
+                                                                        : c.ext_spill ? std::min(c.wide, bn) : bn)
+                                                      : std::min(c.ext_blocks, bn);
+                    HIP_OK(launch_wf_extend(c.ds, WS, b, eb, sm, cs));
+                    if (timed) HIP_OK(hipEventRecord(P.kev[2 * P.ki + 1], cs));
+                    ++P.ki;
+                    HIP_OK(launch_wf_shade(c.ds, WS, b, D, pp.n_items, L.d_rad,
+                                           std::min(sm == kSmFlat ? c.wide : c.shade_blocks, (n + kBlock - 1) / kBlock),
+                                           sm, cs));
+                    P.path_launches += 2;
+                }
+            }
+            join_lanes(L, lanes, L0);  // L0 continues after every lane's chunks
+        }
+        if (timed) HIP_OK(hipEventRecord(P.ev[2 * bi + 1], L0));
+        if (s0 + spb < N) {
+            HIP_OK(launch_accumulate(L.d_rad, L.d_acc, n_pix, nb, s0 == 0, 0, c.fp, c.d_out, nullptr, 0, L0));
+        } else {
+            join_to_end(L, P.stream);
+            accumulate_last(P, L.d_rad, nb, s0 == 0, c.fp, c.d_out);
+        }
+    }
+}
+// A megakernel frame's segments and bytes from its counters (render_finish).
+void count_mega(const Pending& P, rs_render_stats* stats) {
+    for (int i = 0; i < 256; ++i) stats->segments += P.cnt[i];
+    stats->kernel_id = RS_KERNEL_PATH_MEGA;
+    stats->kernel_bytes += 24ull * P.n_pix * P.N * P.n_frames;  // radiance out, 3 x f64 per sample
+}
+// A bounce-synchronous frame's segments and bytes from its queue counters (render_finish).
+void count_batched(const rs_scene* s, const Pending& P, rs_render_stats* stats) {
+    // segments = sum over chunks and bounces of the extend queue lengths; the extend reads a ray
+    // (2 x 32 B records) and writes a hit (16 B) per segment
+    uint64_t seg = 0;
+    for (uint64_t c = 0; c < P.n_chunks_total; ++c)
+        for (uint32_t b = 0; b < P.depth; ++b) seg += P.qc[c * (P.depth + 1) + b];
+#ifdef RS_DEV_KNOBS
+    if (s->dump_iters)
+        for (uint32_t b = 0; b < P.depth; ++b) {
+            uint64_t nb = 0;
+            for (uint64_t c = 0; c < P.n_chunks_total; ++c) nb += P.qc[c * (P.depth + 1) + b];
+            std::fprintf(stderr, "bounce %2u: %11llu paths\n", b, (unsigned long long)nb);
+        }
+#endif
+    stats->kernel_id = RS_KERNEL_WF_EXTEND;
+    stats->kernel_bytes += 80ull * seg;
+    stats->segments += seg;
+}
+
 // Enqueue the rows `rows` of the frame on replica R (its device must be current): camera samples ->
 // wavefront (streaming or bounce-synchronous) or megakernel -> ordered accumulation -> into_color into
 // d_out (W*H RGBA on R's device), the last step on `S`, the stream the frame ends on. The path work
@@ -1746,12 +2245,13 @@ void render_enqueue(const rs_scene* s, Replica& R, const rs_camera_desc* cam, co
     P.R = &R;
     P.stream = S;
     P.timed = timed;
-    P.counted = counted = counted || timed;
+    P.counted = counted || timed;
     const uint32_t n_rows = rows.count();
     if (n_rows == 0) return;
     P.empty = false;
+    FrameConsts c{};
     // one frame at a time for trees whose traversal stack spills to the replica's shared HBM overflow
-    const bool ext_spill = s->stack_need > stack_lds(s->scene_mode);
+    c.ext_spill = s->stack_need > stack_lds(s->scene_mode);
     const uint32_t n_slots = frame_slots(s);
     Slot& L = R.slots[R.next_slot % n_slots];
     R.next_slot = (R.next_slot + 1) % n_slots;
@@ -1762,10 +2262,7 @@ void render_enqueue(const rs_scene* s, Replica& R, const rs_camera_desc* cam, co
     // the slot's previous frame must be done with its buffers; the caller's earlier work must be
     // done when the kernels read the caller's memory (the mask); a timed frame runs alone
     if (L.free_rec) HIP_OK(hipStreamWaitEvent(L0, L.free_ev, 0));
-    if (d_mask || timed) {
-        HIP_OK(hipEventRecord(L.entry_ev, S));
-        HIP_OK(hipStreamWaitEvent(L0, L.entry_ev, 0));
-    }
+    if (d_mask || timed) join(L.entry_ev, S, L0);
     if (timed)
         for (Slot& o : R.slots)
             if (&o != &L && o.free_rec) HIP_OK(hipStreamWaitEvent(L0, o.free_ev, 0));
@@ -1780,415 +2277,57 @@ void render_enqueue(const rs_scene* s, Replica& R, const rs_camera_desc* cam, co
     const uint32_t N = sq * sq;
     const uint32_t D = st->depth;
 
-    DCamera dc = make_camera(*cam);
-    PathParams pp{};
+    c.dc = make_camera(*cam);
+    PathParams& pp = c.pp;
     pp.n_pix_local = n_pix; pp.width = W; pp.height = H; pp.row_begin = rows.begin; pp.row_step = rows.step;
     pp.sqrt_spp = sq; pp.depth = D;
     pp.key_base = splitmix64_h(splitmix64_h(st->seed) ^ (uint64_t)st->pass);
     pp.mask = d_mask;
-    FinalParams fp;
+    FinalParams& fp = c.fp;
     fp.n_pix_local = n_pix; fp.width = W; fp.row_begin = rows.begin; fp.row_step = rows.step; fp.n_samples = N;
     fp.gamma = st->gamma; fp.mask = d_mask;
 
-    const uint32_t spb = N ? (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(N, s->max_items_per_batch / n_pix)) : 0;
-    const uint32_t n_batches = spb ? (N + spb - 1) / spb : 0;
+    c.spb = N ? (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(N, s->max_items_per_batch / n_pix)) : 0;
     ensure(L, L.d_acc, L.acc_cap, (size_t)3 * n_pix);
     if (!L.d_cnt) HIP_OK(hipMalloc((void**)&L.d_cnt, 512 * sizeof(unsigned long long)));
     // launch grids: grid-stride kernels over at most these many blocks (shading grids and the
     // streaming extend: 64 per CU; 8 -> 64 measured 9.22 -> 9.12 ms on the bench frame in round 2)
-    const uint32_t wide = (uint32_t)std::max(1, R.n_cu * 64);
+    c.wide = (uint32_t)std::max(1, R.n_cu * 64);
     // the streaming extend: one block per 256 paths (a grid-stride loop over fewer blocks waits at the
     // queue barriers for its slowest wave, batch after batch); a bounded grid where the traversal stack
     // spills to the HBM overflow array, which is sized by grid threads
-    const uint32_t ext_cap = ext_spill ? wide : 0xFFFFFFFFu;
-    const uint32_t ext_blocks = (uint32_t)std::max(1, R.n_cu * std::max(1, R.ext_bpc));
-    const uint32_t shade_blocks = (uint32_t)std::max(1, R.n_cu * std::max(1, R.shade_bpc));
-    ensure_stack_overflow(s, R, (uint64_t)std::max(std::max(ext_blocks, shade_blocks), wide) * kBlock);
-    const SceneRef ds = R.ref();
-    P.rec_bytes = tag_in_ray(ds) ? 96u : 104u;
-    const int sm = s->scene_mode;
-
-    auto new_ev = [&]() { hipEvent_t e; HIP_OK(hipEventCreate(&e)); return e; };
-    // the frame's end on S: join L0 into S, then the last accumulate there (it writes the caller's frame)
-    auto join_to_S = [&]() {
-        if (S == L0) return;
-        HIP_OK(hipEventRecord(L.join_ev[0], L0));
-        HIP_OK(hipStreamWaitEvent(S, L.join_ev[0], 0));
-    };
-    size_t ki = 0;
-    uint32_t path_launches = 0;
-    size_t n_counts = 0;
-
-    if (N == 0) {  // no samples: into_color of 0 / 0 (NaN, or 0 with the mask) for every lattice pixel
-        HIP_OK(hipMemsetAsync(L.d_acc, 0, (size_t)3 * n_pix * sizeof(double), L0));
-        join_to_S();
-        HIP_OK(launch_finalize(L.d_acc, d_out, fp, S));
-    } else if (streaming) {
-        const uint32_t want = ext_spill ? 1u : std::min<uint32_t>(kMaxLanes, s->stream_lanes);
-        uint64_t pool = pool_limit(s, R, want);
-        FrameSched f = make_sched(s, n_pix, N, D, want, pool, n_frames);
-        auto rad_n = [&]() { return (size_t)3 * f.ring * f.B; };
-        // the smallest pool a frame is scheduled on: 64 Ki camera samples per iteration (or the whole frame); below
-        // that the iterations (and their counter blocks) multiply, and the render reports the device as full
-        const uint64_t pool_min = std::min<uint64_t>(f.cap, (uint64_t)65536 * std::max<uint32_t>(D, 1));
-        if (f.cap > L.wf_cap || f.lanes > L.wf_lanes || rad_n() > L.rad_cap) {
-            // the slot allocates: as much as the device has free
-            const uint64_t fp = std::max(pool_min, pool_limit_free(s, R, L, want, rad_n() * sizeof(double)));
-            if (fp < pool) { pool = fp; f = make_sched(s, n_pix, N, D, want, pool, n_frames); }
-        }
-        // an allocation that still fails (memory taken meanwhile): both buffers back, half the pool
-        while (!carve_wf(L, f.cap, f.lanes) || !try_ensure(L, L.d_rad, L.rad_cap, rad_n())) {
-            release_pool(L);
-            if (pool <= pool_min) throw Error(RS_E_NOMEM, "device memory exhausted: no room for the frame's path pool");
-            pool = std::max<uint64_t>(pool_min, pool / 2);
-            f = make_sched(s, n_pix, N, D, want, pool, n_frames);
-        }
-        f.keys.resize(n_frames);
-        for (uint32_t k = 0; k < n_frames; ++k)
-            f.keys[k] = splitmix64_h(splitmix64_h(st->seed) ^ (uint64_t)(st->pass + k));
-        n_counts = f.n_counts;
-        uint32_t* const prev_counts = L.d_counts;
-        ensure(L, L.d_counts, L.counts_cap, n_counts);
-        if (L.d_counts != prev_counts) L.counts_clean = 0;
-        if (n_counts > L.counts_clean) HIP_OK(hipMemsetAsync(L.d_counts, 0, n_counts * sizeof(uint32_t), L0));
-        L.counts_clean = 0;
-        // Carried-extend grids. Without history a carried launch takes a block per 256 of the paths injected in the
-        // last depth - 1 iterations (the bound on what it can carry), though from the second bounce on it carries a
-        // few of them (bench frame: 28 % at t = 2, 3 % at t = 7): the empty blocks only read the count and leave, but
-        // their dispatch costs a launch some microseconds. A frame of the same shape as one completed earlier takes
-        // that frame's count of the iteration + 25 % + 16 Ki paths (blocks grid-stride over what exceeds it, so the
-        // frame never depends on the estimate). The counts reach pinned host memory at the end of each frame
-        // (Slot::h_hist) and are read here without waiting (bench frame 6.47 -> 6.39 ms with a fixed cap,
-        // profiles/r6/ab/carried_cap_r6g1.txt).
-        uint64_t sig = splitmix64_h(((uint64_t)n_pix << 32) ^ N) ^ splitmix64_h(((uint64_t)D << 40) ^ ((uint64_t)f.lanes << 32) ^ n_frames);
-        std::vector<size_t> hoff(f.lanes, 0);
-        size_t hwords = 0;
-        for (uint32_t l = 0; l < f.lanes; ++l) {
-            const LaneSched& ln = f.lane[l];
-            sig = splitmix64_h(sig ^ ln.Q ^ (ln.T << 40) ^ (ln.total << 1) ^ (uint64_t)ln.finish);
-            hoff[l] = hwords;
-            hwords += 2 * ln.T;  // per iteration: the paths carried in, the paths queued for shading
-        }
-        for (Slot& o : R.slots) {
-            if (!o.hist_pending) continue;
-            const hipError_t q = hipEventQuery(o.hist_ev);
-            if (q == hipSuccess) {
-                o.hist_pending = false;
-                R.hist.assign(o.h_hist, o.h_hist + o.hist_words);
-                R.hist_sig = o.hist_sig;
-            } else {
-                (void)hipGetLastError();  // hipErrorNotReady: not an error here
-                if (q != hipErrorNotReady) HIP_OK(q);
-            }
-        }
-#ifdef RS_NO_GRID_HINT  // (dev A/B: every carried launch over a block per 256 paths of the window)
-        const bool hint = false;
-#else
-        const bool hint = R.hist_sig == sig && R.hist.size() == hwords;
-#endif
-        if (L.hist_cap < hwords) {
-            if (L.h_hist) { HIP_OK(hipEventSynchronize(L.hist_ev)); HIP_OK(hipHostFree(L.h_hist)); L.h_hist = nullptr; }
-            HIP_OK(hipHostMalloc((void**)&L.h_hist, hwords * sizeof(uint32_t)));
-            L.hist_cap = hwords;
-            L.hist_pending = false;
-        }
-        if (!L.hist_ev) HIP_OK(hipEventCreateWithFlags(&L.hist_ev, hipEventDisableTiming));
-        // every lane and the accumulate stream start after L0's dependencies and the counter reset
-        hipStream_t ls[kMaxLanes] = {L0};
-        for (uint32_t l = 1; l < f.lanes; ++l) ls[l] = lane_stream(L, l);
-        if (!L.acc_stream) HIP_OK(hipStreamCreateWithFlags(&L.acc_stream, hipStreamNonBlocking));
-        if (!L.fork_ev) HIP_OK(hipEventCreateWithFlags(&L.fork_ev, hipEventDisableTiming));
-        HIP_OK(hipEventRecord(L.fork_ev, L0));
-        for (uint32_t l = 1; l < f.lanes; ++l) HIP_OK(hipStreamWaitEvent(ls[l], L.fork_ev, 0));
-        HIP_OK(hipStreamWaitEvent(L.acc_stream, L.fork_ev, 0));
-        if (n_frames > 1) HIP_OK(hipStreamWaitEvent(L.acc_stream, outs_after, 0));
-        // per batch: its paths are done (recorded on its lane) / it has been accumulated (acc stream)
-        while (L.bev.size() < 2 * (size_t)f.n_batches) {
-            hipEvent_t e;
-            HIP_OK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-            L.bev.push_back(e);
-        }
-        auto done_ev = [&](uint32_t k) { return L.bev[2 * (size_t)k]; };
-        auto acc_ev = [&](uint32_t k) { return L.bev[2 * (size_t)k + 1]; };
-        // (a multi-pass stream's iterations carry paths and inject camera samples: two launches, each part at its own
-        // occupancy -- 30 share frames of the bench frame 0.971 -> 0.909 ms, profiles/r6/passes)
-        const bool split = ext_split(sm) || s->ext_split || n_frames > 1;
-        // lean / heavy shading launches (spheres mode; nest modes with an LDS image) pay one more launch tail per
-        // iteration: worth it on full frames (bench 7.16 -> 7.09 ms), not on small ones (the N = 8 row share, 3.2 M
-        // samples: 1.013 -> 1.066 ms)
-        const bool split_shade = s->shade_split && (uint64_t)n_pix * N >= kSplitShadeMin;
-        size_t n_ext = 0;
-        for (const LaneSched& ln : f.lane) n_ext += ln.T * (split ? 2 : 1);
-        P.kev.assign(timed ? 2 * n_ext : 0, nullptr);
-        for (auto& e : P.kev) e = new_ev();
-        P.ev.assign(timed ? 2 : 0, nullptr);  // path_ms: the frame's iterations
-        for (auto& e : P.ev) e = new_ev();
-        if (timed) HIP_OK(hipEventRecord(P.ev[0], L0));
-        P.lanes.assign(f.lane.begin(), f.lane.end());
-        // per lane: the samples injected by its last depth - 1 iterations (a bound on the paths it
-        // carries into the next one), its next batch to be done, and the injections per iteration
-        std::vector<uint64_t> window(f.lanes, 0), m_done(f.lanes, 0);
-        std::vector<std::vector<uint32_t>> inj(f.lanes);
-        for (uint32_t l = 0; l < f.lanes; ++l) inj[l].assign(f.lane[l].T, 0u);
-        walk(f,
-             [&](uint32_t l, uint64_t t) {
-                 const LaneSched& ln = f.lane[l];
-                 const hipStream_t cs = ls[l];
-                 WfState WS = L.lane_ws[l];
-                 WS.tagw = tag_in_ray(ds);
-                 WS.counts = L.d_counts + ln.cnt_off;
-                 QEnt** qd = L.d_qptrs[l];
-                 const uint32_t n_new = ln.n_new(t);
-                 inj[l][t] = n_new;
-                 InjParams I = inj_params(f, ln, t);
-                 if (n_new) {
-                     const uint64_t m = t * ln.Q / f.B;
-                     // a batch taking over a ring buffer: after the batch `ring` earlier was accumulated
-                     for (uint64_t mm = m; mm <= m + 1 && mm < ln.batch.size(); ++mm) {
-                         const uint32_t kk = ln.batch[mm];
-                         if (ln.first_it(mm) == t && kk >= f.ring) HIP_OK(hipStreamWaitEvent(cs, acc_ev(kk - f.ring), 0));
-                     }
-                 }
-                 if (ln.finish && t + 1 == ln.T) {  // the finish: every carried path to its end, one launch
-                     const uint32_t b = (uint32_t)std::min<uint64_t>(wide, (window[l] + kBlock - 1) / kBlock);
-                     // timed with the extends: it traces the World::hit of every segment it runs (the statistics
-                     // count them on this iteration), so the dominant kernel's time covers the frame's segments
-                     if (timed) HIP_OK(hipEventRecord(P.kev[2 * ki], cs));
-                     HIP_OK(launch_wfs_finish(ds, WS, (uint32_t)t, D, L.d_rad, std::max<uint32_t>(1, b), sm, cs));
-                     if (timed) HIP_OK(hipEventRecord(P.kev[2 * ki + 1], cs));
-                     ++ki;
-                     ++path_launches;
-                     window[l] = 0;
-                     while (m_done[l] < ln.batch.size() && ln.done_it(m_done[l]) == t)
-                         HIP_OK(hipEventRecord(done_ev(ln.batch[m_done[l]++]), cs));
-                     return;
-                 }
-                 auto extend = [&](int part, uint64_t n_max) {
-                     if (hint && part == kExtCarried) {
-                         const uint64_t est = R.hist[hoff[l] + 2 * t];
-                         n_max = std::min<uint64_t>(n_max, est + est / 4 + 64ull * kBlock);
-                     }
-                     const uint32_t b = (uint32_t)std::min<uint64_t>(ext_cap, (n_max + kBlock - 1) / kBlock);
-                     if (!b) return;
-                     HIP_OK(launch_wfs_extend(ds, dc, pp, WS, qd, (uint32_t)t, I, L.d_rad, b, part, sm, cs,
-                                              timed ? P.kev[2 * ki] : nullptr, timed ? P.kev[2 * ki + 1] : nullptr));
-                     ++ki;
-                     ++path_launches;
-                 };
-                 // an iteration with only carried paths (or only camera samples) runs the kernel compiled for
-                 // that part alone: nest-0 example.sdl 8.95 -> 8.41 ms; the spheres mode's carried part runs at 5
-                 // waves (ext_min_waves), bench frame 7.58 -> 7.31 ms (profiles/r5/ab; at 4 waves its parts had
-                 // measured 2.8 % slower than the merged kernel, profiles/r4/ab/part_pick)
-                 if (split) {
-                     extend(kExtCarried, window[l]);
-                     extend(kExtCamera, n_new);
-                 } else if (n_new == 0) {
-                     extend(kExtCarried, window[l]);
-                 } else if (window[l] == 0) {
-                     extend(kExtCamera, n_new);
-                 } else {
-                     extend(kExtAll, window[l] + n_new);
-                 }
-                 if (D > 0) {
-                     uint64_t n_sh = window[l] + n_new;  // the paths it may shade: at most the live ones
-#ifndef RS_NO_SHADE_HINT  // (dev A/B)
-                     if (hint && cam_fused(sm, kExtCamera)) {
-                         // the camera launch shades most of its hits itself: the grid from the earlier frame's
-                         // queued count of the iteration (k_wfs_shade_all writes it next to the carried count)
-                         const uint64_t est = R.hist[hoff[l] + 2 * t + 1];
-                         n_sh = std::min<uint64_t>(n_sh, est + est / 4 + 64ull * kBlock);
-                     } else if (hint) {
-                         const uint64_t est = R.hist[hoff[l] + 2 * t];
-                         n_sh = std::min<uint64_t>(n_sh, est + est / 4 + 64ull * kBlock + n_new);
-                     }
-#endif
-                     const uint32_t b = (uint32_t)std::min<uint64_t>(wide, (n_sh + kBlock - 1) / kBlock);
-                     HIP_OK(launch_wfs_shade_all(ds, WS, qd, s->class_mask, (uint32_t)t, D, L.d_rad, b,
-                                                 split_shade, sm, cs));
-                     ++path_launches;
-                 }
-                 // carried into t + 1: the samples injected by iterations t - depth + 2 .. t
-                 window[l] += n_new;
-                 if (D == 0) window[l] = 0;
-                 else if (t + 1 >= D) window[l] -= inj[l][t + 1 - D];
-                 while (m_done[l] < ln.batch.size() && ln.done_it(m_done[l]) == t)
-                     HIP_OK(hipEventRecord(done_ev(ln.batch[m_done[l]++]), cs));
-             },
-             [&](uint32_t k) {
-                 // batch k's samples have all finished: accumulate in sample order (the last batch on S,
-                 // writing the frame and zeroing the counters for the next frame unless statistics read them;
-                 // an earlier pass's last batch into its frame, on the accumulate stream)
-                 const uint32_t fr = k / f.nbpf, kl = k % f.nbpf;
-                 float* const out = n_frames > 1 ? outs[fr] : d_out;
-                 const uint32_t planes = (uint32_t)(std::min<uint64_t>(f.B, (uint64_t)n_pix * N - (uint64_t)kl * f.B) / n_pix);
-                 const double* rk = L.d_rad + (size_t)3 * (k % f.ring) * f.B;  // item-major radiance (put_rad)
-                 if (k + 1 < f.n_batches) {
-                     HIP_OK(hipStreamWaitEvent(L.acc_stream, done_ev(k), 0));
-                     HIP_OK(launch_accumulate(rk, L.d_acc, n_pix, planes, kl == 0, kl + 1 == f.nbpf ? 1 : 0, fp, out,
-                                              nullptr, 0, L.acc_stream));
-                     HIP_OK(hipEventRecord(acc_ev(k), L.acc_stream));
-                 } else {
-                     HIP_OK(hipEventRecord(L.join_ev[0], L.acc_stream));
-                     HIP_OK(hipStreamWaitEvent(S, L.join_ev[0], 0));
-                     HIP_OK(hipStreamWaitEvent(S, done_ev(k), 0));
-                     for (uint32_t l = 1; l < f.lanes; ++l) {  // (every lane's last iteration, for the counters)
-                         HIP_OK(hipEventRecord(L.join_ev[l], ls[l]));
-                         HIP_OK(hipStreamWaitEvent(S, L.join_ev[l], 0));
-                     }
-                     HIP_OK(hipEventRecord(L.fork_ev, L0));
-                     HIP_OK(hipStreamWaitEvent(S, L.fork_ev, 0));
-                     // the frame's carried and queued counts (words 0 and 1 of each lane's iterations' counter blocks)
-                     // for later frames' grids, before the accumulate zeroes them
-                     for (uint32_t l = 0; l < f.lanes; ++l)
-                         HIP_OK(hipMemcpy2DAsync(L.h_hist + hoff[l], 2 * sizeof(uint32_t), L.d_counts + f.lane[l].cnt_off,
-                                                 kWfsStride * sizeof(uint32_t), 2 * sizeof(uint32_t), f.lane[l].T,
-                                                 hipMemcpyDeviceToHost, S));
-                     HIP_OK(hipEventRecord(L.hist_ev, S));
-                     L.hist_pending = true;
-                     L.hist_sig = sig;
-                     L.hist_words = hwords;
-                     const size_t nz = counted ? 0 : n_counts;
-                     HIP_OK(launch_accumulate(rk, L.d_acc, n_pix, planes, kl == 0, 1, fp, out, L.d_counts,
-                                              (uint32_t)nz, S));
-                     L.counts_clean = nz;
-                 }
-             });
-        P.inj = std::move(inj);
-        if (timed) HIP_OK(hipEventRecord(P.ev[1], S));
-    } else {
-        // bounce-synchronous wavefront (flat / rich scenes) or megakernel: per batch of spb sample planes
-        ensure(L, L.d_rad, L.rad_cap, (size_t)3 * n_pix * spb);
-        // Wavefront lanes (rs_scene_set_lanes, default 2): a batch's chunks go round-robin to lane streams
-        // and run concurrently, so one lane's launch tails and small late-bounce launches overlap the
-        // other's work. Chunks are whole sample planes when the batch allows (camera-ray tile order,
-        // gen_perm). Scenes whose traversal stack spills to HBM keep one lane (the overflow array is
-        // shared by blockIdx).
-        const uint32_t want = (wavefront && !ext_spill) ? std::min<uint32_t>(kMaxLanes, s->wf_lanes) : 1u;
-        uint32_t lanes = want;
-        uint64_t chunk = 0, n_chunks_total = 0;
-        auto plan = [&](uint64_t pool) {  // chunks of at most `pool` paths per lane
-            lanes = want;
-            chunk = std::max<uint64_t>(kBlock, std::min<uint64_t>(pool, (uint64_t)n_pix * spb));
-            if (lanes > 1) {
-                const uint64_t planes = (spb + lanes - 1) / lanes;
-                const uint64_t split = std::max<uint64_t>(kBlock, spb >= lanes ? (uint64_t)n_pix * planes
-                                                                               : ((uint64_t)n_pix * spb + lanes - 1) / lanes);
-                chunk = std::min(chunk, split);
-            }
-            n_chunks_total = 0;
-            for (uint32_t s0 = 0; s0 < N; s0 += spb) n_chunks_total += ((uint64_t)n_pix * std::min(spb, N - s0) + chunk - 1) / chunk;
-            if (n_chunks_total < lanes) lanes = std::max<uint32_t>(1, (uint32_t)n_chunks_total);
-        };
-        uint64_t pool = pool_limit(s, R, want);
-        plan(pool);
-        hipStream_t ls[kMaxLanes] = {L0};
-        if (wavefront) {
-            const uint64_t pool_min = std::min<uint64_t>(chunk, 1ull << 20);  // chunks of at least 1 Mi paths
-            if (chunk > L.wf_cap || lanes > L.wf_lanes) {  // the slot allocates: as much as the device has free
-                const uint64_t fp = std::max(pool_min, pool_limit_free(s, R, L, want, L.rad_cap * sizeof(double)));
-                if (fp < pool) plan(pool = fp);  // (the slot's radiance buffer, allocated above, stays)
-            }
-            while (!carve_wf(L, chunk, lanes)) {
-                if (pool <= pool_min) throw Error(RS_E_NOMEM, "device memory exhausted: no room for the frame's path pool");
-                plan(pool = std::max<uint64_t>(pool_min, pool / 2));
-            }
-            n_counts = (size_t)n_chunks_total * (D + 1);
-            uint32_t* const prev_counts = L.d_counts;
-            ensure(L, L.d_counts, L.counts_cap, n_counts);
-            if (L.d_counts != prev_counts) L.counts_clean = 0;
-            for (uint32_t l = 1; l < lanes; ++l) ls[l] = lane_stream(L, l);
-            if (lanes > 1 && !L.fork_ev) HIP_OK(hipEventCreateWithFlags(&L.fork_ev, hipEventDisableTiming));
-        }
-        P.ev.assign(timed ? 2 * (size_t)n_batches : 0, nullptr);
-        for (auto& e : P.ev) e = new_ev();
-        P.kev.assign(timed ? 2 * (wavefront ? (size_t)n_chunks_total * D : n_batches) : 0, nullptr);
-        for (auto& e : P.kev) e = new_ev();
-        if (!wavefront || timed) HIP_OK(hipMemsetAsync(L.d_cnt, 0, 512 * sizeof(unsigned long long), L0));
-        if (n_counts > L.counts_clean) HIP_OK(hipMemsetAsync(L.d_counts, 0, n_counts * sizeof(uint32_t), L0));
-        L.counts_clean = 0;
-        uint32_t bi = 0;
-        uint64_t chunk_i = 0;
-        for (uint32_t s0 = 0; s0 < N; s0 += spb, ++bi) {
-            const uint32_t nb = std::min(spb, N - s0);
-            pp.s0 = s0;
-            pp.n_items = (uint64_t)n_pix * nb;
-            if (timed) HIP_OK(hipEventRecord(P.ev[2 * bi], L0));
-            if (!wavefront) {
-                if (timed) HIP_OK(hipEventRecord(P.kev[2 * ki], L0));
-                HIP_OK(launch_path_mega(ds, dc, pp, sm, L.d_rad, L.d_cnt, wide, L0));
-                if (timed) HIP_OK(hipEventRecord(P.kev[2 * ki + 1], L0));
-                ++ki;
-                ++path_launches;
-            } else {
-                if (lanes > 1) {  // fork: the lane streams start after what L0 holds
-                    HIP_OK(hipEventRecord(L.fork_ev, L0));
-                    for (uint32_t l = 1; l < lanes; ++l) HIP_OK(hipStreamWaitEvent(ls[l], L.fork_ev, 0));
-                }
-                uint32_t lane = 0;
-                for (uint64_t c0 = 0; c0 < pp.n_items; c0 += chunk, ++chunk_i, lane = (lane + 1) % lanes) {
-                    const uint32_t n = (uint32_t)std::min<uint64_t>(chunk, pp.n_items - c0);
-                    WfState WS = L.lane_ws[lane];
-                    WS.tagw = tag_in_ray(ds);
-                    WS.counts = L.d_counts + chunk_i * (D + 1);
-                    const hipStream_t cs = ls[lane];
-                    // a pixel mask: k_wf_gen compacts the live samples into set 0's shards (counts from zero)
-                    if (pp.mask) HIP_OK(hipMemsetAsync(WS.heads, 0, 8 * 32 * sizeof(uint32_t), cs));
-                    HIP_OK(launch_wf_gen(dc, pp, WS, c0, n, L.d_rad, cs));
-                    ++path_launches;
-                    for (uint32_t b = 0; b < D; ++b) {
-                        if (timed) HIP_OK(hipEventRecord(P.kev[2 * ki], cs));
-                        // meshes: one block per 256 paths (C5 49.6 -> 48.1 ms), at most 64 per CU where the tree
-                        // spills its stack to HBM (the overflow array is sized for that grid; a grid of resident
-                        // blocks only, grid-striding, made the C5 extend 35 % slower); the rich mode a bounded grid
-                        const uint32_t bn = (n + kBlock - 1) / kBlock;
-                        // flat scenes on the 4-wide tree: the persistent extend (k_wf_extend_dyn), one resident grid
-                        const uint32_t eb = sm == kSmFlat ? (flat_dyn(ds) ? std::min(ext_blocks, bn)
-                                                                          : ext_spill ? std::min(wide, bn) : bn)
-                                                          : std::min(ext_blocks, bn);
-                        HIP_OK(launch_wf_extend(ds, WS, b, eb, sm, cs));
-                        if (timed) HIP_OK(hipEventRecord(P.kev[2 * ki + 1], cs));
-                        ++ki;
-                        HIP_OK(launch_wf_shade(ds, WS, b, D, pp.n_items, L.d_rad,
-                                               std::min(sm == kSmFlat ? wide : shade_blocks, (n + kBlock - 1) / kBlock),
-                                               sm, cs));
-                        path_launches += 2;
-                    }
-                }
-                if (lanes > 1) {  // join: L0 continues after every lane's chunks
-                    for (uint32_t l = 1; l < lanes; ++l) {
-                        HIP_OK(hipEventRecord(L.join_ev[l], ls[l]));
-                        HIP_OK(hipStreamWaitEvent(L0, L.join_ev[l], 0));
-                    }
-                }
-            }
-            if (timed) HIP_OK(hipEventRecord(P.ev[2 * bi + 1], L0));
-            const bool last = s0 + spb >= N;
-            if (!last) {
-                HIP_OK(launch_accumulate(L.d_rad, L.d_acc, n_pix, nb, s0 == 0, 0, fp, d_out, nullptr, 0, L0));
-            } else {
-                // the last batch's accumulate finishes the frame (into_color) and, when no statistics
-                // read the queue counters afterwards, zeroes them for the next frame (no memset launch)
-                join_to_S();
-                const size_t nz = (wavefront && !counted) ? n_counts : 0;
-                HIP_OK(launch_accumulate(L.d_rad, L.d_acc, n_pix, nb, s0 == 0, 1, fp, d_out, L.d_counts,
-                                         (uint32_t)nz, S));
-                L.counts_clean = nz;
-            }
-        }
-        P.n_chunks_total = n_chunks_total;
-    }
-    HIP_OK(hipEventRecord(L.free_ev, S));
-    L.free_rec = true;
-    P.kind = !wavefront ? 0 : streaming ? 2 : 1;
+    c.ext_cap = c.ext_spill ? c.wide : 0xFFFFFFFFu;
+    c.ext_blocks = (uint32_t)std::max(1, R.n_cu * std::max(1, R.ext_bpc));
+    c.shade_blocks = (uint32_t)std::max(1, R.n_cu * std::max(1, R.shade_bpc));
+    ensure_stack_overflow(s, R, (uint64_t)std::max(std::max(c.ext_blocks, c.shade_blocks), c.wide) * kBlock);
+    c.ds = R.ref();
+    c.d_out = d_out;
+    c.outs = outs;
+    c.outs_after = outs_after;
+    P.rec_bytes = tag_in_ray(c.ds) ? 96u : 104u;
+    P.kind = !wavefront ? Scheme::Mega : streaming ? Scheme::Streaming : Scheme::Batched;
     P.n_frames = n_frames;
     P.n_pix = n_pix;
     P.N = N;
     P.depth = D;
-    P.n_batches = n_batches;
-    P.ki = ki;
-    P.path_launches = path_launches;
+
+    if (N == 0) enqueue_empty(c, P);
+    else if (streaming) enqueue_streaming(s, st, c, P);
+    else enqueue_batched(s, st, c, P);
+    HIP_OK(hipEventRecord(L.free_ev, S));
+    L.free_rec = true;
 }
 
+// milliseconds between the event pairs ev[2k], ev[2k + 1], k < n
+double elapsed_ms(const std::vector<hipEvent_t>& ev, size_t n) {
+    double sum = 0.0;
+    for (size_t k = 0; k < n; ++k) {
+        float ms = 0;
+        HIP_OK(hipEventElapsedTime(&ms, ev[2 * k], ev[2 * k + 1]));
+        sum += ms;
+    }
+    return sum;
+}
 // Wait for replica P's share and add its statistics into *stats (which the caller zeroed).
 void render_finish(const rs_scene* s, Pending& P, rs_render_stats* stats) {
     if (P.empty) return;
@@ -2199,104 +2338,54 @@ void render_finish(const rs_scene* s, Pending& P, rs_render_stats* stats) {
     // frame, so its slot's counters are final and are read on the slot's own lane stream
     const hipStream_t cs = P.timed ? P.stream : L.lane[0];
     HIP_OK(hipMemcpyAsync(P.cnt, L.d_cnt, sizeof(P.cnt), hipMemcpyDeviceToHost, cs));
-    size_t words = 0;
-    if (P.N > 0 && P.kind == 2)
-        for (const LaneSched& ln : P.lanes) words = std::max<size_t>(words, ln.cnt_off + (ln.T + 1) * kWfsStride);
-    if (P.N > 0 && P.kind == 1) words = (size_t)P.n_chunks_total * (P.depth + 1);
-    P.qc.assign(words, 0u);
-    if (words) HIP_OK(hipMemcpyAsync(P.qc.data(), L.d_counts, words * sizeof(uint32_t), hipMemcpyDeviceToHost, cs));
+    P.qc.assign(P.n_counts, 0u);
+    if (P.n_counts) HIP_OK(hipMemcpyAsync(P.qc.data(), L.d_counts, P.n_counts * sizeof(uint32_t), hipMemcpyDeviceToHost, cs));
     HIP_OK(hipStreamSynchronize(cs));
-    double path_ms = 0.0;
-    for (size_t b = 0; b + 1 < P.ev.size(); b += 2) {
-        float ms = 0;
-        HIP_OK(hipEventElapsedTime(&ms, P.ev[b], P.ev[b + 1]));
-        path_ms += ms;
+    switch (P.kind) {
+    case Scheme::Mega: count_mega(P, stats); break;
+    case Scheme::Batched: count_batched(s, P, stats); break;
+    case Scheme::Streaming: count_streaming(s, P, stats); break;
     }
-    double kernel_ms = 0.0;
-    for (size_t k = 0; P.timed && k < P.ki; ++k) {  // (a counted, untimed frame has no kernel events)
-        float ms = 0;
-        HIP_OK(hipEventElapsedTime(&ms, P.kev[2 * k], P.kev[2 * k + 1]));
-        kernel_ms += ms;
-    }
-    const uint64_t items = (uint64_t)P.n_pix * P.N * P.n_frames;
-    uint64_t seg = 0, kbytes = 0;
-    if (P.kind == 0) {
-        for (int i = 0; i < 256; ++i) seg += P.cnt[i];
-        stats->kernel_id = RS_KERNEL_PATH_MEGA;
-        kbytes = 24ull * items;  // radiance out, 3 x f64 per sample
-    } else if (P.kind == 1) {
-        // segments = sum over chunks and bounces of the extend queue lengths; the extend reads a ray
-        // (2 x 32 B records) and writes a hit (16 B) per segment
-        for (uint64_t c = 0; c < P.n_chunks_total; ++c)
-            for (uint32_t b = 0; b < P.depth; ++b) seg += P.qc[c * (P.depth + 1) + b];
-#ifdef RS_DEV_KNOBS
-        if (s->dump_iters)
-            for (uint32_t b = 0; b < P.depth; ++b) {
-                uint64_t nb = 0;
-                for (uint64_t c = 0; c < P.n_chunks_total; ++c) nb += P.qc[c * (P.depth + 1) + b];
-                std::fprintf(stderr, "bounce %2u: %11llu paths\n", b, (unsigned long long)nb);
-            }
-#endif
-        stats->kernel_id = RS_KERNEL_WF_EXTEND;
-        kbytes = 80ull * seg;
-    } else {
-        // the streaming extend's library byte model, per iteration: ray records in (64 B)
-        // per carried path; the queue entry with the hit (16 B) per queued segment; the record out (96 B + item
-        // + level) per live camera sample (written after its traversal for the ones that go on to the shading
-        // launch, or after its in-place shading for a lean-class hit of the spheres mode's camera launch, whose
-        // survivors write the level-1 record and the others 24 B of radiance: an upper bound); radiance out (24 B)
-        // per path ending in extend unshaded, + its throughput record and item in (36 B); radiance out for masked
-        // samples. `fused`: the camera hits shaded inside the extend (word 1 of the statistics lines): they are
-        // neither queued nor ended there
-        for (size_t l = 0; l < P.lanes.size(); ++l)
-            for (uint64_t t = 0; t < P.lanes[l].T; ++t) {
-                const uint32_t* q = &P.qc[P.lanes[l].cnt_off + t * kWfsStride];
-                uint64_t live_new = 0, shaded = 0, fused = 0;
-                for (uint32_t k = 0; k < kStatLines; ++k) live_new += q[cix(kCntStat0 + (int)k)];
-                for (uint32_t k = 0; k < kStatLines; ++k) fused += q[cix(kCntStat0 + (int)k) + 1];
-                for (int k = 0; k < kWfsClasses; ++k) shaded += q[cix(1 + k)];
-                const uint64_t old = q[cix(0)], live = old + live_new;
-                if (P.lanes[l].finish && t + 1 == P.lanes[l].T) {
-                    // the finish: its carried paths' first segments and (stat lines) the ones after; a record in
-                    // (104 B) and a radiance out (24 B) per path
-                    seg += live;
-                    kbytes += 128ull * old;
-                    continue;
-                }
-                const uint64_t dead_new = P.inj[l][t] - live_new;
-                const uint64_t ended = live - shaded - fused;
-                seg += live;
-                kbytes += 64ull * old + 16ull * shaded + (uint64_t)P.rec_bytes * live_new + 60ull * ended + 24ull * dead_new;
-#ifdef RS_DEV_KNOBS
-                if (s->dump_iters) {
-                    const uint32_t* qn = q + kWfsStride;  // the next set's runs
-                    std::fprintf(stderr, "iter lane %zu t %3llu: carried %9llu (front %9u back %9u) camera %9llu shaded %9llu"
-                                 " [%u %u %u %u %u] fused %9llu ended %9llu -> next front %9u back %9u\n", l, (unsigned long long)t,
-                                 (unsigned long long)old, q[cix(kCntFront)], q[cix(kCntBack)], (unsigned long long)live_new,
-                                 (unsigned long long)shaded, q[cix(1)], q[cix(2)], q[cix(3)], q[cix(4)], q[cix(5)],
-                                 (unsigned long long)fused, (unsigned long long)ended, qn[cix(kCntFront)], qn[cix(kCntBack)]);
-                }
-#endif
-            }
-        stats->kernel_id = RS_KERNEL_WFS_EXTEND;
-    }
-    stats->path_ms += path_ms;
+    stats->path_ms += elapsed_ms(P.ev, P.ev.size() / 2);
     stats->launches += P.path_launches;
     stats->kernel_launches += (uint32_t)P.ki;
-    stats->kernel_ms += kernel_ms;
-    stats->kernel_bytes += kbytes;
-    stats->segments += seg;
+    stats->kernel_ms += elapsed_ms(P.kev, P.timed ? P.ki : 0);  // (a counted, untimed frame has no kernel events)
     stats->tree_arity = s->tree_arity;
-    stats->samples += items;  // masked-out pixels included (they trace nothing)
+    stats->samples += (uint64_t)P.n_pix * P.N * P.n_frames;  // masked-out pixels included (they trace nothing)
 }
 
-// copy rows `rows` of a W-wide RGBA f32 frame between two buffers of the same layout
-hipError_t copy_rows(float* dst, const float* src, uint32_t W, RowSet rows, hipMemcpyKind kind, hipStream_t st) {
-    const uint32_t n = rows.count();
-    if (n == 0) return hipSuccess;
+// A frame that ends on replica R's own stream lives in R's next slot (the slot render_enqueue picks): its
+// previous frame must be done with the slot's frame (d_out, npx pixels) and mask. `mask`: the caller's, copied
+// into the slot's d_mask on R's stream.
+Slot& stage_slot(const rs_scene* s, Replica& R, size_t npx, const uint8_t* mask, hipMemcpyKind kind) {
+    Slot& L = R.slots[R.next_slot % frame_slots(s)];
+    if (L.free_rec) HIP_OK(hipStreamWaitEvent(R.stream, L.free_ev, 0));
+    ensure(L, L.d_out, L.out_cap, npx * 4);
+    if (mask) {
+        ensure(L, L.d_mask, L.mask_cap, npx);
+        HIP_OK(hipMemcpyAsync(L.d_mask, mask, npx, kind, R.stream));
+    }
+    return L;
+}
+// ... and its rows `rows` go from the slot's frame to `dst`, a W-wide RGBA f32 frame of the same layout, on R's stream
+void copy_back(float* dst, Replica& R, Slot& L, uint32_t W, RowSet rows, hipMemcpyKind kind) {
     const size_t row_bytes = (size_t)W * 4 * sizeof(float);
     const size_t off = (size_t)rows.begin * W * 4;
-    return hipMemcpy2DAsync(dst + off, row_bytes * rows.step, src + off, row_bytes * rows.step, row_bytes, n, kind, st);
+    if (rows.count())
+        HIP_OK(hipMemcpy2DAsync(dst + off, row_bytes * rows.step, L.d_out + off, row_bytes * rows.step, row_bytes,
+                                rows.count(), kind, R.stream));
+    HIP_OK(hipEventRecord(L.free_ev, R.stream));  // the copy read the slot's frame
+}
+// drain what was enqueued before the buffers go away (an entry point's error path)
+void drain(const std::vector<Pending>& P) {
+    for (const Pending& p : P)
+        if (p.R) { DeviceGuard g(p.R->device); (void)hipDeviceSynchronize(); }
+}
+// the end of every entry point: the call's statistics, with its wall time since t0
+void report_stats(const rs_scene* s, rs_render_stats acc, std::chrono::steady_clock::time_point t0, rs_render_stats* stats) {
+    acc.tree_arity = s->tree_arity;
+    acc.ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    if (stats) *stats = acc;
 }
 
 // rs_render_device: replica 0 renders its rows straight into d_out, its frame ending on the caller's
@@ -2310,70 +2399,48 @@ void render_frame_device(rs_scene* s, const rs_camera_desc* cam, const rs_render
     const auto t0 = std::chrono::steady_clock::now();
     const uint32_t n = (uint32_t)s->reps.size();
     const size_t npx = (size_t)cam->width * cam->height;
-    std::vector<std::unique_ptr<Pending>> P(n);
-    std::vector<hipEvent_t> done(n, nullptr);
-    hipEvent_t entry = nullptr;  // what the caller queued on `stream` before this call (mask fill, d_out use)
+    std::vector<Pending> P(n);
+    std::vector<Event> done(n);
+    Event entry;  // what the caller queued on `stream` before this call (mask fill, d_out use)
     try {
         if (n > 1) {
             DeviceGuard g(s->reps[0]->device);
-            HIP_OK(hipEventCreateWithFlags(&entry, hipEventDisableTiming));
-            HIP_OK(hipEventRecord(entry, stream));
+            record(entry, stream);
         }
         for (uint32_t k = 0; k < n; ++k) {
             Replica& R = *s->reps[k];
-            P[k].reset(new Pending());
             const RowSet rows = replica_rows(cam, st, k, n);
             DeviceGuard g(R.device);
             if (k == 0) {
-                render_enqueue(s, R, cam, st, rows, d_mask, d_out, stream, *P[k], stats != nullptr, false);
+                render_enqueue(s, R, cam, st, rows, d_mask, d_out, stream, P[k], stats != nullptr, false);
                 continue;
             }
             if (rows.count() == 0) continue;
             // the replica's stream reads d_mask and writes d_out: order it after the caller's work
-            HIP_OK(hipStreamWaitEvent(R.stream, entry, 0));
-            // this frame's copies of the mask and the frame live in R's next slot (the slot render_enqueue
-            // picks): its previous frame must be done with them
-            const uint32_t n_slots = frame_slots(s);
-            Slot& L = R.slots[R.next_slot % n_slots];
-            if (L.free_rec) HIP_OK(hipStreamWaitEvent(R.stream, L.free_ev, 0));
-            ensure(L, L.d_out, L.out_cap, npx * 4);
-            const uint8_t* m = nullptr;
-            if (d_mask) {
-                ensure(L, L.d_mask, L.mask_cap, npx);
-                HIP_OK(hipMemcpyAsync(L.d_mask, d_mask, npx, hipMemcpyDefault, R.stream));
-                m = L.d_mask;
-            }
-            render_enqueue(s, R, cam, st, rows, m, L.d_out, R.stream, *P[k], stats != nullptr, false);
-            HIP_OK(copy_rows(d_out, L.d_out, cam->width, rows, hipMemcpyDefault, R.stream));
-            HIP_OK(hipEventRecord(L.free_ev, R.stream));  // the copy read the slot's frame
-            HIP_OK(hipEventCreateWithFlags(&done[k], hipEventDisableTiming));
-            HIP_OK(hipEventRecord(done[k], R.stream));
+            HIP_OK(hipStreamWaitEvent(R.stream, entry.get(), 0));
+            Slot& L = stage_slot(s, R, npx, d_mask, hipMemcpyDefault);
+            render_enqueue(s, R, cam, st, rows, d_mask ? L.d_mask : nullptr, L.d_out, R.stream, P[k], stats != nullptr, false);
+            copy_back(d_out, R, L, cam->width, rows, hipMemcpyDefault);
+            record(done[k], R.stream);
         }
         {
             DeviceGuard g(s->reps[0]->device);
             for (uint32_t k = 1; k < n; ++k)
-                if (done[k]) HIP_OK(hipStreamWaitEvent(stream, done[k], 0));
+                if (done[k]) HIP_OK(hipStreamWaitEvent(stream, done[k].get(), 0));
         }
         if (stats) {  // without stats the call returns once everything is enqueued (asynchronous)
             for (uint32_t k = 0; k < n; ++k) {
                 DeviceGuard g(s->reps[k]->device);
-                render_finish(s, *P[k], &acc);
+                render_finish(s, P[k], &acc);
             }
             DeviceGuard g(s->reps[0]->device);
             HIP_OK(hipStreamSynchronize(stream));
         }
     } catch (...) {
-        for (uint32_t k = 0; k < n; ++k)  // drain what was enqueued before the buffers go away
-            if (P[k] && P[k]->R) { DeviceGuard g(P[k]->R->device); (void)hipDeviceSynchronize(); }
-        for (hipEvent_t e : done) if (e) (void)hipEventDestroy(e);
-        if (entry) (void)hipEventDestroy(entry);
+        drain(P);
         throw;
     }
-    for (hipEvent_t e : done) if (e) (void)hipEventDestroy(e);
-    if (entry) (void)hipEventDestroy(entry);
-    acc.tree_arity = s->tree_arity;
-    acc.ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    if (stats) *stats = acc;
+    report_stats(s, acc, t0, stats);
 }
 
 // rs_render_device_passes: passes st->pass + k into d_outs[k]. One replica, a streaming scene mode and a pass the
@@ -2424,31 +2491,25 @@ void render_passes_device(rs_scene* s, const rs_camera_desc* cam, const rs_rende
             std::sort(sorted.begin(), sorted.end());
             if (std::adjacent_find(sorted.begin(), sorted.end()) != sorted.end()) groups = 1;
         }
-        std::vector<std::unique_ptr<Pending>> P(groups);
-        hipEvent_t entry = nullptr;  // the caller's work on `stream` before the call: the earlier frames' writes wait
+        std::vector<Pending> P(groups);
+        Event entry;  // the caller's work on `stream` before the call: the earlier frames' writes wait
         try {
-            HIP_OK(hipEventCreateWithFlags(&entry, hipEventDisableTiming));
-            HIP_OK(hipEventRecord(entry, stream));
+            record(entry, stream);
             for (uint32_t k = 0; k < groups; ++k) {
                 const uint32_t lo = (uint32_t)((uint64_t)n * k / groups), hi = (uint32_t)((uint64_t)n * (k + 1) / groups);
                 rs_render_settings sg = *st;
                 sg.pass = st->pass + lo;
-                P[k].reset(new Pending());
-                render_enqueue(s, R, cam, &sg, rows, nullptr, d_outs[lo], stream, *P[k], stats != nullptr, false,
-                               hi - lo, d_outs + lo, entry);
-                if (stats) render_finish(s, *P[k], &acc);
+                render_enqueue(s, R, cam, &sg, rows, nullptr, d_outs[lo], stream, P[k], stats != nullptr, false,
+                               hi - lo, d_outs + lo, entry.get());
+                if (stats) render_finish(s, P[k], &acc);
             }
             if (stats) HIP_OK(hipStreamSynchronize(stream));
         } catch (...) {
             (void)hipDeviceSynchronize();  // drain what was enqueued before the buffers go away
-            if (entry) (void)hipEventDestroy(entry);
             throw;
         }
-        HIP_OK(hipEventDestroy(entry));
     }
-    acc.tree_arity = s->tree_arity;
-    acc.ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    if (stats) *stats = acc;
+    report_stats(s, acc, t0, stats);
 }
 
 // rs_render: every replica renders its rows into a frame on its own device on its own stream; the
@@ -2461,46 +2522,32 @@ void render_frame_host(rs_scene* s, const rs_camera_desc* cam, const rs_render_s
     const auto t0 = std::chrono::steady_clock::now();
     const uint32_t n = (uint32_t)s->reps.size();
     const size_t npx = (size_t)cam->width * cam->height;
-    std::vector<std::unique_ptr<Pending>> P(n);
+    std::vector<Pending> P(n);
     std::vector<RowSet> rows(n);
     std::vector<Slot*> slot(n, nullptr);
     try {
         for (uint32_t k = 0; k < n; ++k) {
             Replica& R = *s->reps[k];
-            P[k].reset(new Pending());
             rows[k] = replica_rows(cam, st, k, n);
             if (rows[k].count() == 0) continue;
             DeviceGuard g(R.device);
-            const uint32_t n_slots = frame_slots(s);
-            Slot& L = R.slots[R.next_slot % n_slots];
+            Slot& L = stage_slot(s, R, npx, mask, hipMemcpyHostToDevice);
             slot[k] = &L;
-            if (L.free_rec) HIP_OK(hipStreamWaitEvent(R.stream, L.free_ev, 0));
-            ensure(L, L.d_out, L.out_cap, npx * 4);
-            const uint8_t* m = nullptr;
-            if (mask) {
-                ensure(L, L.d_mask, L.mask_cap, npx);
-                HIP_OK(hipMemcpyAsync(L.d_mask, mask, npx, hipMemcpyHostToDevice, R.stream));
-                m = L.d_mask;
-            }
-            render_enqueue(s, R, cam, st, rows[k], m, L.d_out, R.stream, *P[k], stats != nullptr, false);
+            render_enqueue(s, R, cam, st, rows[k], mask ? L.d_mask : nullptr, L.d_out, R.stream, P[k], stats != nullptr, false);
         }
         for (uint32_t k = 0; k < n; ++k) {
             if (rows[k].count() == 0) continue;
             Replica& R = *s->reps[k];
             DeviceGuard g(R.device);
-            HIP_OK(copy_rows(out, slot[k]->d_out, cam->width, rows[k], hipMemcpyDeviceToHost, R.stream));
-            HIP_OK(hipEventRecord(slot[k]->free_ev, R.stream));
-            render_finish(s, *P[k], &acc);
+            copy_back(out, R, *slot[k], cam->width, rows[k], hipMemcpyDeviceToHost);
+            render_finish(s, P[k], &acc);
             HIP_OK(hipStreamSynchronize(R.stream));
         }
     } catch (...) {
-        for (uint32_t k = 0; k < n; ++k)
-            if (P[k] && P[k]->R) { DeviceGuard g(P[k]->R->device); (void)hipDeviceSynchronize(); }
+        drain(P);
         throw;
     }
-    acc.tree_arity = s->tree_arity;
-    acc.ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    if (stats) *stats = acc;
+    report_stats(s, acc, t0, stats);
 }
 
 // rs_render_rows: the frame's row lattice in bands, each band a frame of its own on the replicas'
@@ -2517,79 +2564,73 @@ void render_frame_rows(rs_scene* s, const rs_camera_desc* cam, const rs_render_s
     const uint32_t n = (uint32_t)s->reps.size();
     const uint32_t W = cam->width, H = cam->height;
     const size_t npx = (size_t)W * H;
-    const uint32_t rb = st->row_begin, re = st->row_end ? std::min(st->row_end, H) : H;
-    const uint32_t step = st->row_step ? st->row_step : 1;
-    const uint32_t n_rows = rb < re ? (re - rb + step - 1) / step : 0;
+    const RowSet all = replica_rows(cam, st, 0, 1);  // the call's lattice
+    const uint32_t n_rows = all.count();
     if (bands == 0) bands = 16;
     const uint32_t per = std::max<uint32_t>(1, (n_rows + bands - 1) / bands);
     const uint32_t n_bands = n_rows ? (n_rows + per - 1) / per : 0;
     // bands in flight per replica: one per frame slot (a band's statistics are read from its slot's counters,
     // so a second band in the same slot would overwrite them before render_finish reads them)
     const uint32_t ahead = frame_slots(s);
-    float* pinned = nullptr;
-    std::vector<std::unique_ptr<Pending>> P(n_bands);
-    std::vector<hipEvent_t> copied(n_bands, nullptr);
-    std::vector<RowSet> rows(n_bands);
-    std::vector<uint8_t*> d_masks(n, nullptr);
-    auto cleanup = [&]() {
-        for (uint32_t k = 0; k < n; ++k) {
-            DeviceGuard g(s->reps[k]->device);
-            (void)hipStreamSynchronize(s->reps[k]->stream);
-            if (d_masks[k]) (void)hipFree(d_masks[k]);
-        }
-        for (hipEvent_t e : copied) if (e) (void)hipEventDestroy(e);
-        if (pinned) (void)hipHostFree(pinned);
-    };
-    try {
-        HIP_OK(hipHostMalloc((void**)&pinned, npx * 4 * sizeof(float)));
-        std::memcpy(pinned, out, npx * 4 * sizeof(float));  // rows off the lattice keep the caller's values
-        if (mask)
-            for (uint32_t k = 0; k < n; ++k) {  // the mask once per replica, read by all its bands
+    {
+        PinnedMem pinned_mem;
+        std::vector<Pending> P(n_bands);
+        std::vector<Event> copied(n_bands);
+        std::vector<RowSet> rows(n_bands);
+        std::vector<DeviceMem> d_masks(n);
+        // the replicas' streams are idle before any of these goes away, on an error as at the end
+        auto drain_streams = [&]() {
+            for (uint32_t k = 0; k < n; ++k) {
                 DeviceGuard g(s->reps[k]->device);
-                HIP_OK(hipMalloc((void**)&d_masks[k], npx));
-                HIP_OK(hipMemcpyAsync(d_masks[k], mask, npx, hipMemcpyHostToDevice, s->reps[k]->stream));
+                (void)hipStreamSynchronize(s->reps[k]->stream);
             }
-        auto enqueue = [&](uint32_t b) {
-            Replica& R = *s->reps[b % n];
-            DeviceGuard g(R.device);
-            rs_render_settings bs = *st;
-            bs.row_begin = rb + b * per * step;
-            bs.row_end = (uint32_t)std::min<uint64_t>(re, (uint64_t)bs.row_begin + (uint64_t)per * step);
-            bs.row_step = step;
-            rows[b] = replica_rows(cam, &bs, 0, 1);
-            const uint32_t n_slots = frame_slots(s);
-            Slot& L = R.slots[R.next_slot % n_slots];
-            if (L.free_rec) HIP_OK(hipStreamWaitEvent(R.stream, L.free_ev, 0));
-            ensure(L, L.d_out, L.out_cap, npx * 4);
-            P[b].reset(new Pending());
-            render_enqueue(s, R, cam, &bs, rows[b], d_masks[b % n], L.d_out, R.stream, *P[b], false, stats != nullptr);
-            HIP_OK(copy_rows(pinned, L.d_out, W, rows[b], hipMemcpyDeviceToHost, R.stream));
-            HIP_OK(hipEventRecord(L.free_ev, R.stream));  // the copy read the slot's frame
-            HIP_OK(hipEventCreateWithFlags(&copied[b], hipEventDisableTiming));
-            HIP_OK(hipEventRecord(copied[b], R.stream));
         };
-        for (uint32_t b = 0; b < std::min(n_bands, ahead * n); ++b) enqueue(b);
-        for (uint32_t b = 0; b < n_bands; ++b) {
-            {
-                DeviceGuard g(s->reps[b % n]->device);
-                HIP_OK(hipEventSynchronize(copied[b]));
-                if (stats) render_finish(s, *P[b], &acc);  // the band's counts (untimed: bands overlap)
+        try {
+            float* pinned = nullptr;
+            HIP_OK(hipHostMalloc((void**)&pinned, npx * 4 * sizeof(float)));
+            pinned_mem.reset(pinned);
+            std::memcpy(pinned, out, npx * 4 * sizeof(float));  // rows off the lattice keep the caller's values
+            if (mask)
+                for (uint32_t k = 0; k < n; ++k) {  // the mask once per replica, read by all its bands
+                    DeviceGuard g(s->reps[k]->device);
+                    void* m = nullptr;
+                    HIP_OK(hipMalloc(&m, npx));
+                    d_masks[k].reset(m);
+                    HIP_OK(hipMemcpyAsync(m, mask, npx, hipMemcpyHostToDevice, s->reps[k]->stream));
+                }
+            auto enqueue = [&](uint32_t b) {
+                Replica& R = *s->reps[b % n];
+                DeviceGuard g(R.device);
+                rows[b].begin = all.begin + b * per * all.step;
+                rows[b].end = (uint32_t)std::min<uint64_t>(all.end, (uint64_t)rows[b].begin + (uint64_t)per * all.step);
+                rows[b].step = all.step;
+                Slot& L = stage_slot(s, R, npx, nullptr, hipMemcpyHostToDevice);
+                render_enqueue(s, R, cam, st, rows[b], (const uint8_t*)d_masks[b % n].get(), L.d_out, R.stream, P[b],
+                               false, stats != nullptr);
+                copy_back(pinned, R, L, W, rows[b], hipMemcpyDeviceToHost);
+                record(copied[b], R.stream);
+            };
+            for (uint32_t b = 0; b < std::min(n_bands, ahead * n); ++b) enqueue(b);
+            for (uint32_t b = 0; b < n_bands; ++b) {
+                {
+                    DeviceGuard g(s->reps[b % n]->device);
+                    HIP_OK(hipEventSynchronize(copied[b].get()));
+                    if (stats) render_finish(s, P[b], &acc);  // the band's counts (untimed: bands overlap)
+                }
+                if (b + ahead * n < n_bands) enqueue(b + ahead * n);
+                for (uint32_t y = rows[b].begin; y < rows[b].end; y += rows[b].step) {
+                    std::memcpy(out + (size_t)y * W * 4, pinned + (size_t)y * W * 4, (size_t)W * 4 * sizeof(float));
+                    cb(user, y, out + (size_t)y * W * 4, W);
+                }
             }
-            if (b + ahead * n < n_bands) enqueue(b + ahead * n);
-            for (uint32_t y = rows[b].begin; y < rows[b].end; y += rows[b].step) {
-                std::memcpy(out + (size_t)y * W * 4, pinned + (size_t)y * W * 4, (size_t)W * 4 * sizeof(float));
-                cb(user, y, out + (size_t)y * W * 4, W);
-            }
+        } catch (...) {
+            drain_streams();
+            throw;
         }
-    } catch (...) {
-        cleanup();
-        throw;
+        drain_streams();
     }
-    cleanup();
     cb(user, H, nullptr, 0);  // end-of-pass sentinel (painter.rs:332)
-    acc.tree_arity = s->tree_arity;
-    acc.ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    if (stats) *stats = acc;
+    report_stats(s, acc, t0, stats);
 }
 
 }  // namespace

@@ -96,6 +96,14 @@ def test_virtual_devices_rows_mask_and_untouched(gpu):
     others = np.setdiff1d(np.arange(31), rows)
     assert np.all(b[others] == -7.0)                 # rows off the lattice keep the caller's values
     assert np.all(b[rows][mask[rows] == 0] == 0.0)
+    # the same lattice in 5 bands (band b on replica b % 3, one mask copy per replica shared by its bands): the
+    # callback gets the lattice rows in order, then the sentinel; rows off the lattice keep render_rows' zeros
+    seen = []
+    c, sc = ds3.render_rows(cam.desc, st, lambda y, out: seen.append(y), mask, bands=5, stats=True)
+    assert seen == list(rows) + [31]
+    assert np.array_equal(a[rows], c[rows])
+    assert np.all(c[others] == 0.0)
+    assert sc.samples == len(rows) * 50 * 4
 
 
 def test_virtual_devices_render_device(gpu):
@@ -118,6 +126,15 @@ def test_virtual_devices_render_device(gpu):
         assert ds.render_device(cam.desc, st, t.data_ptr(), side.cuda_stream, stats=False) is None
         torch.cuda.current_stream().wait_stream(side)
         assert np.array_equal(t.cpu().numpy(), host), k
+    # a device mask: the second replica renders with its own copy of it
+    mask = (np.indices((40, 64)).sum(0) % 5 != 0).astype(np.uint8)
+    masked, _, _ = _frame(world, cam, st, [0], mask)
+    d_mask = torch.from_numpy(mask).cuda()
+    t.fill_(-1.0)
+    ds.render_device(cam.desc, st, t.data_ptr(), torch.cuda.current_stream().cuda_stream, d_mask.data_ptr())
+    got = t.cpu().numpy()
+    assert np.array_equal(got, masked)
+    assert np.all(got[mask == 0] == 0.0)
 
 
 def test_host_only_commit_refuses_render(gpu):
