@@ -471,6 +471,9 @@ public:
 
     void export_to(SceneSink& sink) const;   // background, time range, world list, lights list
     rs_scene* device_scene();                // exported + committed on first use (BVH build + upload)
+    // ... committed to the listed HIP devices instead (rs_scene_commit_devices; none = a host-only build, whose
+    // renders throw RS_E_STATE); throws RS_E_STATE when the world is already committed
+    rs_scene* device_scene(const std::vector<int>& devices);
     const HittableList& hittables() const { return hittables_; }
     const HittableList& lights() const { return lights_; }
 private:
@@ -548,8 +551,14 @@ public:
     std::vector<Pixel> shot_to_target(const char* path, World& world, PainterTarget* target,
                                       PainterController* controller, const PixelController* pixel_map);
     std::vector<Pixel> shot(const char* path, World& world) { return shot_to_target(path, world, nullptr, nullptr, nullptr); }
+    // The photo's first-hit feature frames (rs_render_features; no reference counterpart): albedo = [r, g, b,
+    // coverage] and normal = [nx, ny, nz, depth], W * H pixels each, with the settings' samples, seed, pass and rows
+    // (depth, gamma and mode do not apply) and pixel_map as the mask.
+    struct Features { std::vector<Pixel> albedo, normal; };
+    Features shot_features(World& world, const PixelController* pixel_map = nullptr);
     const rs_render_stats& last_stats() const { return stats_; }
 private:
+    std::vector<uint8_t> mask_of(const PixelController* pixel_map) const;
     Camera camera_;
     uint32_t depth_ = 8, samples_ = 50, pass_ = 0, row_begin_ = 0, row_end_ = 0, row_step_ = 1;
     bool gamma_ = true;

@@ -192,6 +192,7 @@ typedef struct rs_render_settings {
 #define RS_KERNEL_PATH_MEGA  1  /* k_path_mega: whole path per thread */
 #define RS_KERNEL_WF_EXTEND  2  /* k_wf_extend: wavefront traversal (generic scenes) */
 #define RS_KERNEL_WFS_EXTEND 3  /* k_wfs_extend: wavefront traversal + material classification */
+#define RS_KERNEL_FEATURES   4  /* k_features: first-hit feature buffers (rs_render_features) */
 typedef struct rs_render_stats {
     uint64_t samples;    /* camera samples traced */
     uint64_t segments;   /* world.hit calls (path segments) */
@@ -349,6 +350,39 @@ int rs_render_device(rs_scene* s, const rs_camera_desc* cam, const rs_render_set
  * counterpart as one call: the reference renders its passes one after the other (raysnail.rs:379). */
 int rs_render_device_passes(rs_scene* s, const rs_camera_desc* cam, const rs_render_settings* st, uint32_t n_passes,
                             float* const* d_outs_rgba, void* stream, rs_render_stats* stats);
+
+/* ---- first-hit feature buffers (guides for a denoiser, a compositor, edge-aware noise maps; no reference
+ * counterpart) ----
+ * Two RGBA f32 frames in the beauty frame's layout: out_albedo = [r, g, b, coverage], out_normal = [nx, ny, nz,
+ * depth]. Either may be NULL (not written); both NULL is RS_E_INVALID. Sample s of pixel (x, y), pix = y W + x, with
+ * sqrt_spp = floor(sqrt(samples)), N = sqrt_spp^2, si = s % sqrt_spp, sj = s / sqrt_spp:
+ *   camera sample   the stratum centre, painter.rs:133-139 / :167-170 with both jitter draws 0.5, in f64:
+ *                   xo = x + (si + 0.5) / sqrt_spp, yo = y + (sj + 0.5) / sqrt_spp, u = xo / W, v = (H - 1 - yo) / H
+ *   ray             Camera::ray(u, v, rng) from the start of the stream seed_from_u64(rs_stream_key(seed, pass, pix,
+ *                   s)): the lens disk and shutter time of the beauty frame's camera (depth of field and motion blur
+ *                   stay; a pinhole camera's guides are noise-free)
+ *   first hit       World::hit(ray, 0.0001, +inf) with medium key 0 (rs_probe_world_hit's convention): a
+ *                   ConstantMedium stops a feature ray at the fixed key-0 distance
+ *   on a hit        normal = HitRecord.normal, depth = t1 (ray directions are unit vectors), coverage = 1, albedo =
+ *                   the f32 colour of the hit's material (the world's white Lambertian where the object has none),
+ *                   widened to f64: Lambertian / Metal / DiffuseMetal / BlinnPhong texture.color(u, v, point);
+ *                   Dielectric / Isotropic texture.even; DiffuseLight its texture's colour without the multiplier;
+ *                   MixedMaterial its material_1's (as settings() chooses, mixed_material.rs:56-58; no RNG draw)
+ *   on a miss       0 in all 8 channels (the background is not composited: coverage lets the caller do it)
+ * Each channel of a pixel is the f64 sum over s = 0 .. N-1 in that order, starting from +0.0, divided by (double)N,
+ * cast to f32: channels are premultiplied by coverage; no gamma. Masked pixels are [0,0,0,0] in both frames; rows
+ * off the row lattice are not written. st->depth, gamma and mode are ignored (mode must still be a valid RS_MODE_*).
+ * Validation as rs_render (RS_E_STATE before commit or on a host-only scene), before anything touches the device.
+ * Several devices: the row lattice is split and gathered as rs_render's; frames are bitwise independent of it.
+ * stats: samples, segments (world.hit calls: one per sample of an unmasked pixel), the kernel's launches and device
+ * time, kernel_id RS_KERNEL_FEATURES. Additive extension of ABI 6. */
+int rs_render_features(rs_scene* s, const rs_camera_desc* cam, const rs_render_settings* st, const uint8_t* mask,
+                       float* out_albedo, float* out_normal, rs_render_stats* stats);
+/* the same into device frames; pointers, stream and stats semantics as rs_render_device (asynchronous when
+ * stats == NULL) */
+int rs_render_features_device(rs_scene* s, const rs_camera_desc* cam, const rs_render_settings* st,
+                              const uint8_t* d_mask, float* d_out_albedo, float* d_out_normal, void* stream,
+                              rs_render_stats* stats);
 
 /* ---- progressive passes (the CLI's pass loop, src/bin/raysnail.rs:311-427) ----
  * Device-resident frames (RGBA f32, W*H*4), all work on the caller's stream (NULL = default). */

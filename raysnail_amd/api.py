@@ -633,6 +633,41 @@ class DeviceScene:
                                                           stream_ptr or None, C.byref(out) if stats else None), "rs_")
         return out
 
+    def render_features(self, cam: A.rs_camera_desc, st: A.rs_render_settings, mask: Optional[np.ndarray] = None,
+                        albedo: Optional[np.ndarray] = None, normal: Optional[np.ndarray] = None,
+                        want: Tuple[bool, bool] = (True, True)):
+        """rs_render_features: the first-hit feature frames (albedo = [r, g, b, coverage], normal = [nx, ny, nz,
+        depth]; (H, W, 4) float32 each) and the call's stats. want: which of the two to render (the other is
+        None); albedo / normal: frames to write into (rows off the lattice keep their values)."""
+        H, W = cam.height, cam.width
+        outs = []
+        for buf, on in ((albedo, want[0]), (normal, want[1])):
+            if on and buf is None:
+                buf = np.zeros((H, W, 4), dtype=np.float32)
+            if not on:
+                buf = None
+            assert buf is None or (buf.shape == (H, W, 4) and buf.dtype == np.float32 and buf.flags.c_contiguous)
+            outs.append(buf)
+        mptr = None
+        if mask is not None:
+            mask = np.ascontiguousarray(mask, dtype=np.uint8).reshape(H * W)
+            mptr = mask.ctypes.data_as(C.c_void_p)
+        stats = A.rs_render_stats()
+        ptrs = [None if b is None else b.ctypes.data_as(C.c_void_p) for b in outs]
+        _check(self.lib, self.lib.rs_render_features(self.handle, C.byref(cam), C.byref(st), mptr, ptrs[0], ptrs[1],
+                                                     C.byref(stats)), "rs_")
+        return outs[0], outs[1], stats
+
+    def render_features_device(self, cam: A.rs_camera_desc, st: A.rs_render_settings, d_albedo_ptr: int,
+                               d_normal_ptr: int, stream_ptr: int = 0, d_mask_ptr: int = 0, stats: bool = True):
+        """rs_render_features_device: the feature frames into device memory (either pointer may be 0). stats as
+        render_device."""
+        out = A.rs_render_stats() if stats else None
+        _check(self.lib, self.lib.rs_render_features_device(self.handle, C.byref(cam), C.byref(st), d_mask_ptr or None,
+                                                            d_albedo_ptr or None, d_normal_ptr or None,
+                                                            stream_ptr or None, C.byref(out) if stats else None), "rs_")
+        return out
+
 
 # ----------------------------------------------------------------------------- camera ----
 class Camera:
@@ -794,6 +829,18 @@ class TakePhotoSettings:
             target.register_pixels(y, out[y])
         out, self.last_stats = world.device_scene().render_rows(cam, st, on_row, mask)
         return out
+
+    def shot_features(self, world: World, pixel_map: Optional[PixelController] = None) -> Tuple[np.ndarray, np.ndarray]:
+        """The first-hit feature frames of the photo (no reference counterpart): albedo = [r, g, b, coverage] and
+        normal = [nx, ny, nz, depth], (H, W, 4) float32 each, with the settings' samples, seed, pass and rows
+        (depth, gamma and mode do not apply) and pixel_map as the mask."""
+        cam = self.camera.desc
+        mask = None
+        if pixel_map is not None and type(pixel_map) is not PixelController:
+            mask = np.array([[1 if pixel_map.calculate_pixel(x, y) else 0 for x in range(cam.width)]
+                             for y in range(cam.height)], dtype=np.uint8)
+        albedo, normal, self.last_stats = world.device_scene().render_features(cam, self.settings(), mask)
+        return albedo, normal
 
     def shot(self, path, world: World) -> np.ndarray:
         """src/camera.rs:290-295 (path is ignored upstream too)."""

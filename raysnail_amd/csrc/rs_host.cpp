@@ -173,6 +173,7 @@ struct Slot {
     unsigned long long* d_cnt = nullptr;     // megakernel segment counters (512)
     uint8_t* d_mask = nullptr; size_t mask_cap = 0;   // replicas > 0: the caller's mask copied over
     float* d_out = nullptr; size_t out_cap = 0;       // replicas > 0 / rs_render: the frame on this device
+    float* d_feat = nullptr; size_t feat_cap = 0;     // likewise the two feature frames (albedo, then normal)
     // wavefront path state (capacity wf_cap paths per set) per lane + queue counters
     void* d_wf = nullptr; size_t wf_cap = 0; uint32_t wf_lanes = 0; size_t wf_bytes = 0;
     QEnt** d_qptrs[kMaxLanes] = {nullptr};        // per lane: device array of the per-class queues
@@ -200,7 +201,7 @@ struct Slot {
             if (lane[l]) (void)hipStreamSynchronize(lane[l]);
         if (acc_stream) (void)hipStreamSynchronize(acc_stream);
         if (free_rec) (void)hipEventSynchronize(free_ev);
-        for (void* p : {(void*)d_rad, (void*)d_acc, (void*)d_cnt, (void*)d_mask, (void*)d_out, d_wf, (void*)d_counts})
+        for (void* p : {(void*)d_rad, (void*)d_acc, (void*)d_cnt, (void*)d_mask, (void*)d_out, (void*)d_feat, d_wf, (void*)d_counts})
             if (p) (void)hipFree(p);
         for (uint32_t l = 0; l < kMaxLanes; ++l) {
             if (lane[l]) (void)hipStreamDestroy(lane[l]);
@@ -2550,6 +2551,150 @@ void render_frame_host(rs_scene* s, const rs_camera_desc* cam, const rs_render_s
     report_stats(s, acc, t0, stats);
 }
 
+// rs_render_features (host = true: every replica renders its rows into frames on its own device on its own stream,
+// the rows are copied back) and rs_render_features_device (replica 0 writes its rows straight into the caller's
+// frames on the caller's stream, the others copy theirs in): the row lattice is split over the replicas as the
+// beauty frame's is. One k_features launch per replica; no path state, no radiance buffers. A replica that does
+// not write in place takes its next frame slot's buffers (Slot::d_feat, d_mask) and waits for that slot's previous
+// frame; so does every replica whose tree spills the kernel's LDS stack to the replica's shared overflow array
+// (frame_slots is 1 there: such frames run one after the other).
+void render_features(rs_scene* s, const rs_camera_desc* cam, const rs_render_settings* st, const uint8_t* mask,
+                     float* out_albedo, float* out_normal, hipStream_t stream, bool host, rs_render_stats* stats) {
+    if (!out_albedo && !out_normal) throw Error(RS_E_INVALID, "null argument: both feature frames");
+    validate_render(s, cam, st);
+    rs_render_stats acc{};
+    const auto t0 = std::chrono::steady_clock::now();
+    const uint32_t n = (uint32_t)s->reps.size();
+    const uint32_t W = cam->width;
+    const size_t npx = (size_t)W * cam->height;
+    const uint32_t sq = (uint32_t)std::floor(std::sqrt((double)st->samples));  // painter.rs:110-118
+    struct Part {
+        hipStream_t S = nullptr;
+        RowSet rows;
+        DeviceMem cnt;
+        Event e0, e1;
+    };
+    std::vector<Part> P(n);
+    std::vector<Event> done(n);
+    Event entry;  // what the caller queued on `stream` before this call (mask fill, use of the frames)
+    auto timed_event = [](Event& e, hipStream_t S) {
+        hipEvent_t h;
+        HIP_OK(hipEventCreate(&h));
+        e.reset(h);
+        HIP_OK(hipEventRecord(h, S));
+    };
+    try {
+        if (!host && n > 1) {
+            DeviceGuard g(s->reps[0]->device);
+            record(entry, stream);
+        }
+        for (uint32_t k = 0; k < n; ++k) {
+            Replica& R = *s->reps[k];
+            Part& p = P[k];
+            p.rows = replica_rows(cam, st, k, n);
+            if (p.rows.count() == 0) continue;
+            DeviceGuard g(R.device);
+            const bool direct = !host && k == 0;
+            p.S = direct ? stream : R.stream;
+            if (!host && k > 0) HIP_OK(hipStreamWaitEvent(p.S, entry.get(), 0));
+            Slot* L = nullptr;
+            if (!direct || s->stack_need > kStackMax) {
+                const uint32_t n_slots = frame_slots(s);
+                L = &R.slots[R.next_slot % n_slots];
+                R.next_slot = (R.next_slot + 1) % n_slots;
+                if (!L->free_ev) HIP_OK(hipEventCreateWithFlags(&L->free_ev, hipEventDisableTiming));
+                if (L->free_rec) HIP_OK(hipStreamWaitEvent(p.S, L->free_ev, 0));
+            }
+            const uint8_t* d_mask = mask;
+            float *d_a = out_albedo, *d_n = out_normal;
+            if (!direct) {
+                ensure(*L, L->d_feat, L->feat_cap, npx * 8);
+                d_a = out_albedo ? L->d_feat : nullptr;
+                d_n = out_normal ? L->d_feat + npx * 4 : nullptr;
+                if (mask) {
+                    ensure(*L, L->d_mask, L->mask_cap, npx);
+                    HIP_OK(hipMemcpyAsync(L->d_mask, mask, npx, host ? hipMemcpyHostToDevice : hipMemcpyDefault, p.S));
+                    d_mask = L->d_mask;
+                }
+            }
+            PathParams pp{};
+            pp.n_pix_local = (uint32_t)((uint64_t)p.rows.count() * W);
+            pp.width = W; pp.height = cam->height; pp.row_begin = p.rows.begin; pp.row_step = p.rows.step;
+            pp.sqrt_spp = sq;
+            pp.key_base = splitmix64_h(splitmix64_h(st->seed) ^ (uint64_t)st->pass);
+            pp.mask = d_mask;
+            // the grid bound of the beauty frame's launches (render_enqueue), so the overflow array is sized once
+            const uint32_t wide = (uint32_t)std::max(1, R.n_cu * 64);
+            const uint32_t grid = std::max(std::max((uint32_t)std::max(1, R.n_cu * std::max(1, R.ext_bpc)),
+                                                    (uint32_t)std::max(1, R.n_cu * std::max(1, R.shade_bpc))), wide);
+            ensure_stack_overflow(s, R, (uint64_t)grid * kBlock);
+            const SceneRef ds = R.ref();
+            if (stats) {
+                void* c = nullptr;
+                HIP_OK(hipMalloc(&c, sizeof(unsigned long long)));
+                p.cnt.reset(c);
+                HIP_OK(hipMemsetAsync(c, 0, sizeof(unsigned long long), p.S));
+                timed_event(p.e0, p.S);
+            }
+            HIP_OK(launch_features(ds, make_camera(*cam), pp, d_a, d_n, (unsigned long long*)p.cnt.get(), s->scene_mode, wide,
+                                   p.S));
+            if (stats) timed_event(p.e1, p.S);
+            if (!direct) {
+                const hipMemcpyKind kind = host ? hipMemcpyDeviceToHost : hipMemcpyDefault;
+                const size_t row_bytes = (size_t)W * 4 * sizeof(float);
+                const size_t off = (size_t)p.rows.begin * W * 4;
+                if (out_albedo)
+                    HIP_OK(hipMemcpy2DAsync(out_albedo + off, row_bytes * p.rows.step, d_a + off, row_bytes * p.rows.step,
+                                            row_bytes, p.rows.count(), kind, p.S));
+                if (out_normal)
+                    HIP_OK(hipMemcpy2DAsync(out_normal + off, row_bytes * p.rows.step, d_n + off, row_bytes * p.rows.step,
+                                            row_bytes, p.rows.count(), kind, p.S));
+                if (!host) record(done[k], p.S);
+            }
+            if (L) {
+                HIP_OK(hipEventRecord(L->free_ev, p.S));
+                L->free_rec = true;
+            }
+        }
+        if (!host) {
+            DeviceGuard g(s->reps[0]->device);
+            for (uint32_t k = 1; k < n; ++k)
+                if (done[k]) HIP_OK(hipStreamWaitEvent(stream, done[k].get(), 0));
+        }
+        if (host || stats) {  // the device call without stats returns once everything is enqueued (asynchronous)
+            for (uint32_t k = 0; k < n; ++k) {
+                Part& p = P[k];
+                if (p.rows.count() == 0) continue;
+                DeviceGuard g(s->reps[k]->device);
+                HIP_OK(hipStreamSynchronize(p.S));
+                if (!stats) continue;
+                unsigned long long segs = 0;
+                HIP_OK(hipMemcpy(&segs, p.cnt.get(), sizeof(segs), hipMemcpyDeviceToHost));
+                float ms = 0;
+                HIP_OK(hipEventElapsedTime(&ms, p.e0.get(), p.e1.get()));
+                const uint64_t pix = (uint64_t)p.rows.count() * W;
+                acc.samples += pix * sq * sq;  // masked-out pixels included (they trace nothing)
+                acc.segments += segs;
+                acc.path_ms += ms; acc.kernel_ms += ms;
+                acc.launches += 1; acc.kernel_launches += 1;
+                acc.kernel_bytes += pix * ((out_albedo ? 16u : 0u) + (out_normal ? 16u : 0u) + (mask ? 1u : 0u));
+            }
+            if (!host && stats) {
+                DeviceGuard g(s->reps[0]->device);
+                HIP_OK(hipStreamSynchronize(stream));
+            }
+        }
+    } catch (...) {
+        for (uint32_t k = 0; k < n; ++k) {  // drain what was enqueued before the buffers go away
+            DeviceGuard g(s->reps[k]->device);
+            (void)hipDeviceSynchronize();
+        }
+        throw;
+    }
+    acc.kernel_id = RS_KERNEL_FEATURES;
+    report_stats(s, acc, t0, stats);
+}
+
 // rs_render_rows: the frame's row lattice in bands, each band a frame of its own on the replicas'
 // frame slots (band b on replica b % n), up to frames_in_flight bands in flight per replica; each
 // band's rows are copied to pinned host memory on the replica's stream, and once a band's copy is
@@ -2957,6 +3102,20 @@ int rs_render_device_passes(rs_scene* s, const rs_camera_desc* cam, const rs_ren
                             float* const* d_outs, void* stream, rs_render_stats* stats) {
     return run([&] {
         render_passes_device(S(s), cam, st, n_passes, d_outs, (hipStream_t)stream, stats);
+    });
+}
+
+int rs_render_features(rs_scene* s, const rs_camera_desc* cam, const rs_render_settings* st, const uint8_t* mask,
+                       float* out_albedo, float* out_normal, rs_render_stats* stats) {
+    return run([&] {
+        render_features(S(s), cam, st, mask, out_albedo, out_normal, nullptr, true, stats);
+    });
+}
+
+int rs_render_features_device(rs_scene* s, const rs_camera_desc* cam, const rs_render_settings* st, const uint8_t* d_mask,
+                              float* d_out_albedo, float* d_out_normal, void* stream, rs_render_stats* stats) {
+    return run([&] {
+        render_features(S(s), cam, st, d_mask, d_out_albedo, d_out_normal, (hipStream_t)stream, false, stats);
     });
 }
 

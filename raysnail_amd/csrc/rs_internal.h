@@ -213,6 +213,11 @@ hipError_t launch_noise(const float* px, int w, int h, float t, uint8_t* redo, u
                         unsigned long long* count, hipStream_t st);
 hipError_t launch_probe_hit(const SceneRef& s, const double* rays, uint32_t n, double tmin, double tmax, double* out, int sm,
                             hipStream_t st);
+// First-hit feature buffers (k_features): the lattice pixels of p (n_pix_local, width, height, row_begin, row_step,
+// sqrt_spp, key_base, mask) into the full frames out_albedo = [r, g, b, coverage] and out_normal = [nx, ny, nz, depth]
+// (RGBA f32; either may be null). seg_counter (may be null): += the world.hit calls. At most max_blocks blocks.
+hipError_t launch_features(const SceneRef& s, const DCamera& c, const PathParams& p, float* out_albedo, float* out_normal,
+                           unsigned long long* seg_counter, int sm, uint32_t max_blocks, hipStream_t st);
 // acc[c * n_pix + pixel] += sum over the batch's samples in sample order (deterministic; item-major
 // radiance rad[3 * item + c], items sample-plane by sample-plane); the last batch writes into_color of the sum into the frame instead (k_finalize's
 // arithmetic, one launch less) and zeroes zero[0, n_zero) (the frame's queue counters) for the next

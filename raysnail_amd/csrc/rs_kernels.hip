@@ -22,7 +22,8 @@
 // Translation units (Makefile): the scene-mode templates of the path kernels are compiled once per
 // mode, in parallel. RS_TU undefined: everything in one unit (tools/regs.sh, build_variant.sh);
 // RS_TU = -1: the common unit (mode-independent kernels, the launchers that dispatch on the scene
-// mode); RS_TU = k >= 0: scene mode k's launch_*_sm<k> instantiations only. RS_TU_SUFFIX names the
+// mode); RS_TU = k >= 0: scene mode k's launch_*_sm<k> instantiations only; RS_TU = 6: the feature
+// unit (k_features with the generic World::hit; no scene mode's launchers). RS_TU_SUFFIX names the
 // unit in its exported debug symbol (nothing, _c, _<k>).
 #define RS_PASTE_(a, b) a##b
 #define RS_PASTE(a, b) RS_PASTE_(a, b)
@@ -34,6 +35,10 @@
 #define RS_TU_COMMON 1
 #define RS_TU_MODES 0
 #define RS_TU_SUFFIX _c
+#elif RS_TU == 6
+#define RS_TU_COMMON 0
+#define RS_TU_MODES 0
+#define RS_TU_SUFFIX _6
 #else
 #define RS_TU_COMMON 0
 #define RS_TU_MODES 1
@@ -2228,6 +2233,156 @@ __global__ __launch_bounds__(kBlock) void k_probe_sample(const DScene* __restric
     out[4 * (size_t)i + 3] = (double)segs;
 }
 
+#if !defined(RS_TU) || RS_TU == 5 || RS_TU == 6
+// First-hit feature buffers: per pixel the mean over its N samples of the camera ray's first hit --
+// albedo and coverage into one RGBA f32 frame, shading normal and depth into another. Sample s of pixel p is the
+// centre of its stratum (painter.rs:133-139, :167-170 with both jitter draws 0.5); its ray is Camera::ray drawn from
+// the start of the sample's stream, its hit World::hit(ray, 0.0001, inf) with medium key 0 (k_probe_hit's convention).
+// SM: kSmGeneric (the feature unit: it serves every scene mode's trees) or kSmMarch (that mode's unit).
+
+// the albedo of the material a hit record carries: what its ScatterRecord's colour would be (DiffuseLight: its
+// texture without the multiplier); MixedMaterial -> material_1 (mixed_material.rs:56-58 settings()), no RNG draw
+__device__ __forceinline__ void first_hit_albedo(const DScene& S, const Hit& h, float c[3]) {
+    int mi = h.mat >= 0 ? h.mat : S.default_mat;
+    for (int k = 0; k < 16 && S.mats[mi].kind == RS_MAT_MIXED; ++k) mi = S.mats[mi].mix_a;
+    const DMaterial& M = S.mats[mi];
+    if (M.kind == RS_MAT_DIELECTRIC || M.kind == RS_MAT_ISOTROPIC) {
+        c[0] = M.even[0]; c[1] = M.even[1]; c[2] = M.even[2];
+    } else {
+        tex_color<1>(S, M, h, c);
+    }
+}
+
+// A wave traces nc = min(N, 64) samples of each of 64 / nc consecutive lattice pixels per chunk (one pixel's camera
+// rays walk nearly the same nodes), N > 64 in chunks of 64 samples of one pixel. The lanes' 8 channels
+// go through LDS ([channel][lane]); lane (pixel, channel) adds its pixel's samples in sample order, starting from
+// +0.0 (a running sum across chunks), and the pixel is written once: two float4 stores. The block's four waves
+// step through the loop together (block barriers around the LDS hand-over), a block per four wave groups.
+// (two waves per SIMD like the generic k_probe_hit; the marcher's out-of-line functions leave its variant one)
+template <int SM>
+__global__ __launch_bounds__(kBlock, SM == kSmMarch ? 1 : 2) void k_features(
+    const DScene* __restrict__ Sp, DCamera C, PathParams P, float4* __restrict__ out_albedo,
+    float4* __restrict__ out_normal, unsigned long long* __restrict__ seg_counter) {
+    const DScene& S = *Sp;  // the scene lives in device memory: no by-value copy in scratch
+    __shared__ int stk_all[kStackMax * kBlock];
+    __shared__ double red_all[kBlock / 64][8 * 64];
+    __shared__ float4 res_all[kBlock / 64][2 * 64];
+    const Stk stk = make_stk(S, stk_all);
+    const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    double* const red = red_all[wave];
+    float* const res = reinterpret_cast<float*>(res_all[wave]);
+    const uint32_t N = P.sqrt_spp * P.sqrt_spp;
+    const uint32_t nc = N < 64 ? (N ? N : 1u) : 64u;  // samples of a pixel per chunk
+    const uint32_t ppw = 64 / nc;                     // pixels per wave group
+    const uint32_t n_chunks = (N + 63) / 64;
+    const uint64_t n_groups = ((uint64_t)P.n_pix_local + ppw - 1) / ppw;
+    const uint64_t n_gblocks = (n_groups + kBlock / 64 - 1) / (kBlock / 64);
+    const uint32_t lp = lane / nc, ls = lane - lp * nc;  // this lane's pixel of the group and sample of the chunk
+    const double sq = (double)P.sqrt_spp, hh = (double)P.height;
+    uint32_t segs = 0;
+    for (uint64_t gb = blockIdx.x; gb < n_gblocks; gb += gridDim.x) {
+        const uint64_t pl0 = (gb * (kBlock / 64) + wave) * ppw;  // the group's first lattice pixel
+        const uint64_t pl = pl0 + lp;
+        bool live = lp < ppw && pl < P.n_pix_local;
+        uint32_t x = 0, y = 0;
+        uint64_t pix = 0;
+        if (live) {
+            x = (uint32_t)(pl % P.width);
+            y = P.row_begin + (uint32_t)(pl / P.width) * P.row_step;
+            pix = (uint64_t)y * P.width + x;
+            live = !P.mask || P.mask[pix];  // painter.rs:204-210: a masked pixel traces nothing
+        }
+        double carry = 0.0;  // N > 64 (one pixel per wave): lane c's running sum of channel c
+        for (uint32_t ch = 0; ch < n_chunks; ++ch) {
+            const uint32_t s = ch * 64 + ls;
+            double f[8] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};  // a miss adds 0.0 to every channel
+            if (live && s < N) {
+                Rng rng;
+                rng.seed_from_u64(splitmix64(splitmix64(P.key_base ^ pix) ^ (uint64_t)s));
+                const uint32_t si = s % P.sqrt_spp, sj = s / P.sqrt_spp;
+                const double xo = (double)x + ((double)si + 0.5) / sq;
+                const double yo = (double)y + ((double)sj + 0.5) / sq;
+                const Ray r = camera_ray(C, xo / (double)P.width, (hh - 1.0 - yo) / hh, rng);  // medium key 0
+                Hit h;
+                ++segs;
+                if (world_hit<SM>(S, r, 0.0001, h, stk)) {
+                    float c[3];
+                    first_hit_albedo(S, h, c);
+                    f[0] = (double)c[0]; f[1] = (double)c[1]; f[2] = (double)c[2]; f[3] = 1.0;
+                    f[4] = h.n.x; f[5] = h.n.y; f[6] = h.n.z; f[7] = h.t1;
+                }
+            }
+#pragma unroll
+            for (int c = 0; c < 8; ++c) red[c * 64 + lane] = f[c];
+            __syncthreads();
+            const uint32_t cnt = N - ch * 64 < nc ? N - ch * 64 : nc;  // samples in this chunk
+            for (uint32_t pc = lane; pc < ppw * 8; pc += 64) {         // (pixel of the group, channel)
+                const double* src = red + (pc & 7u) * 64 + (pc >> 3) * nc;
+                double a = ch ? carry : 0.0;
+                for (uint32_t k = 0; k < cnt; ++k) a += src[k];
+                carry = a;
+                if (ch + 1 == n_chunks) res[pc] = (float)(a / (double)N);
+            }
+            __syncthreads();
+        }
+        if (n_chunks == 0) {  // no samples: 0 / 0, as the beauty frame's into_color
+            for (uint32_t pc = lane; pc < ppw * 8; pc += 64) res[pc] = (float)(0.0 / (double)N);
+            __syncthreads();
+        }
+        // the group's pixels: lanes [0, ppw) the albedo frame's float4, [ppw, 2 ppw) the normal frame's
+        for (uint32_t q = lane; q < 2 * ppw; q += 64) {
+            const uint32_t which = q >= ppw ? 1u : 0u, p = q - which * ppw;
+            const uint64_t qpl = pl0 + p;
+            float4* const o = which ? out_normal : out_albedo;
+            if (qpl < P.n_pix_local && o) {
+                const uint32_t qx = (uint32_t)(qpl % P.width);
+                const uint32_t qy = P.row_begin + (uint32_t)(qpl / P.width) * P.row_step;
+                const uint64_t qpix = (uint64_t)qy * P.width + qx;
+                float4 v = res_all[wave][p * 2 + which];
+                if (P.mask && !P.mask[qpix]) v = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+                o[qpix] = v;
+            }
+        }
+        // (the next group's barriers separate these reads of res from its writes)
+    }
+    if (seg_counter) {  // statistics: world.hit calls, one atomic per wave
+        unsigned long long s64 = segs;
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) s64 += __shfl_xor(s64, off, 64);
+        if (lane == 0 && s64) atomicAdd(seg_counter, s64);
+    }
+}
+
+// blocks: at most the grid the caller sized the stack overflow for (grid-stride over the wave groups)
+template <int SM>
+static hipError_t features_launch(const SceneRef& s, const DCamera& c, const PathParams& p, float* out_albedo,
+                                  float* out_normal, unsigned long long* seg_counter, uint32_t max_blocks, hipStream_t st) {
+    const uint32_t N = p.sqrt_spp * p.sqrt_spp;
+    const uint32_t ppw = 64 / (N < 64 ? (N ? N : 1u) : 64u);
+    const uint64_t groups = ((uint64_t)p.n_pix_local + ppw - 1) / ppw;
+    const uint64_t blocks = std::min<uint64_t>((groups + kBlock / 64 - 1) / (kBlock / 64), max_blocks);
+    if (!blocks) return hipSuccess;
+    hipLaunchKernelGGL(k_features<SM>, dim3((uint32_t)blocks), dim3(kBlock), 0, st, s.dev, c, p,
+                       reinterpret_cast<float4*>(out_albedo), reinterpret_cast<float4*>(out_normal), seg_counter);
+    return hipGetLastError();
+}
+#if !defined(RS_TU) || RS_TU == 5
+hipError_t features_march(const SceneRef& s, const DCamera& c, const PathParams& p, float* out_albedo, float* out_normal,
+                          unsigned long long* seg_counter, uint32_t max_blocks, hipStream_t st) {
+    return features_launch<kSmMarch>(s, c, p, out_albedo, out_normal, seg_counter, max_blocks, st);
+}
+#endif
+#if !defined(RS_TU) || RS_TU == 6
+hipError_t features_march(const SceneRef& s, const DCamera& c, const PathParams& p, float* out_albedo, float* out_normal,
+                          unsigned long long* seg_counter, uint32_t max_blocks, hipStream_t st);
+hipError_t launch_features(const SceneRef& s, const DCamera& c, const PathParams& p, float* out_albedo, float* out_normal,
+                           unsigned long long* seg_counter, int sm, uint32_t max_blocks, hipStream_t st) {
+    if (sm == kSmMarch) return features_march(s, c, p, out_albedo, out_normal, seg_counter, max_blocks, st);
+    return features_launch<kSmGeneric>(s, c, p, out_albedo, out_normal, seg_counter, max_blocks, st);
+}
+#endif
+#endif  // the feature unit or the marcher unit
+
 // ---- launchers ----
 // Mode-dependent launchers: launch_X_sm<SM> (defined and instantiated per mode unit) behind a
 // dispatcher on the scene mode (common unit).
@@ -2398,7 +2553,7 @@ hipError_t wfs_shade_all_sm(const SceneRef& s, const WfState& w, QEnt* const* qu
 }
 #endif  // RS_TU_MODES
 
-#if defined(RS_TU) && RS_TU >= 0  // this unit's mode
+#if defined(RS_TU) && RS_TU >= 0 && RS_TU_MODES  // this unit's mode
 #define RS_INSTANTIATE_SM(R, NAME, PARAMS, ARGS) template R NAME##_sm<RS_TU> PARAMS;
 RS_SM_LAUNCHERS(RS_INSTANTIATE_SM)
 #if RS_TU == 1 || RS_TU == 3 || RS_TU == 4  // the streaming-wavefront modes

@@ -308,19 +308,29 @@ void World::export_to(SceneSink& sink) const {
         for (uint32_t h : sink.object(o)) sink.check(sink.api.lights_add(sink.scene, h));
 }
 
-rs_scene* World::device_scene() {
-    if (scene_) return scene_;
+// export the world into a new scene and commit it: to the current device, or to `devices` when given
+static rs_scene* commit_world(const World& w, const std::vector<int>* devices) {
     rs_scene* s = nullptr;
     check_rs(rs_scene_create(&s));
     try {
         SceneSink sink(hip_sink_api(), s);
-        export_to(sink);
-        check_rs(rs_scene_commit(s));
+        w.export_to(sink);
+        check_rs(devices ? rs_scene_commit_devices(s, devices->data(), (int)devices->size()) : rs_scene_commit(s));
     } catch (...) {
         rs_scene_destroy(s);
         throw;
     }
-    scene_ = s;
+    return s;
+}
+
+rs_scene* World::device_scene() {
+    if (!scene_) scene_ = commit_world(*this, nullptr);
+    return scene_;
+}
+
+rs_scene* World::device_scene(const std::vector<int>& devices) {
+    if (scene_) throw Error(RS_E_STATE, "world already committed");
+    scene_ = commit_world(*this, &devices);
     return scene_;
 }
 
@@ -359,16 +369,35 @@ rs_render_settings TakePhotoSettings::settings() const {
     return st;
 }
 
-std::vector<Pixel> TakePhotoSettings::shot_to_target(const char*, World& world, PainterTarget* target,
-                                                     PainterController*, const PixelController* pixel_map) {
-    const rs_camera_desc& cam = camera_.desc();
-    const size_t W = cam.width, H = cam.height;
+// PixelController::calculate_pixel for every pixel (painter.rs:204-210); empty without a controller
+std::vector<uint8_t> TakePhotoSettings::mask_of(const PixelController* pixel_map) const {
+    const size_t W = camera_.desc().width, H = camera_.desc().height;
     std::vector<uint8_t> mask;
     if (pixel_map) {
         mask.resize(W * H);
         for (size_t y = 0; y < H; ++y)
             for (size_t x = 0; x < W; ++x) mask[y * W + x] = pixel_map->calculate_pixel(x, y) ? 1 : 0;
     }
+    return mask;
+}
+
+TakePhotoSettings::Features TakePhotoSettings::shot_features(World& world, const PixelController* pixel_map) {
+    const rs_camera_desc& cam = camera_.desc();
+    const size_t npx = (size_t)cam.width * cam.height;
+    const std::vector<uint8_t> mask = mask_of(pixel_map);
+    Features f{std::vector<Pixel>(npx, Pixel{0.f, 0.f, 0.f, 0.f}), std::vector<Pixel>(npx, Pixel{0.f, 0.f, 0.f, 0.f})};
+    const rs_render_settings st = settings();
+    check_rs(rs_render_features(world.device_scene(), &cam, &st, mask.empty() ? nullptr : mask.data(),
+                                reinterpret_cast<float*>(f.albedo.data()), reinterpret_cast<float*>(f.normal.data()),
+                                &stats_));
+    return f;
+}
+
+std::vector<Pixel> TakePhotoSettings::shot_to_target(const char*, World& world, PainterTarget* target,
+                                                     PainterController*, const PixelController* pixel_map) {
+    const rs_camera_desc& cam = camera_.desc();
+    const size_t W = cam.width, H = cam.height;
+    const std::vector<uint8_t> mask = mask_of(pixel_map);
     std::vector<Pixel> out(W * H, Pixel{0.f, 0.f, 0.f, 0.f});
     const rs_render_settings st = settings();
     const uint8_t* mp = mask.empty() ? nullptr : mask.data();

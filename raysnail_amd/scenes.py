@@ -549,3 +549,36 @@ def materials_scene(width: int = 96, height: int = 64):
     cam = CameraBuilder().look_from(Point3(9.0, 3.0, 7.0)).look_at(Point3(0.0, 0.8, 0.0)).fov(35.0) \
         .aperture(0.02).focus(10.0).width(width).height(height).build()
     return cam, World(h, lights, Gradient(C32(0.3, 0.4, 0.5), C32(0.7, 0.89, 1.0)), (0.0, 0.0))
+
+
+def features_scene(width: int = 48, height: int = 30):
+    """Build-owned fixture of the first-hit feature buffers (rs_render_features): one object per way a hit record
+    gets its material and normal -- a checker ground sphere small enough to leave sky in the frame, Metal,
+    Dielectric, DiffuseLight (also the light), MixedMaterial and material-less spheres, a moving sphere, a Box, an
+    xz AARect, a Quadric-and-Box Intersection under a rotated and translated TfFacade, and a Difference. The camera
+    has a wide lens (aperture 0.1) and an open shutter (1.0), so the guides carry depth of field and motion blur."""
+    from .api import MixedMaterial
+    h = HittableList()
+    h.add(Sphere((0.0, -100.0, 0.0), 100.0, Lambertian(Checker(C32(0.2, 0.3, 0.1), C32(0.9, 0.9, 0.9), 3.0))))
+    h.add(Sphere((-3.0, 0.8, 1.0), 0.8, Metal(C32(0.8, 0.8, 0.9))))
+    h.add(Sphere((3.0, 0.7, 2.5), 0.7, Dielectric(C32(0.9, 1.0, 0.8), 1.5).reflect_curve(Glass())))
+    light = Sphere((0.5, 3.6, -2.0), 0.9, DiffuseLight(C32(1.0, 0.9, 0.7)).multiplier(4.0))
+    h.add(light)
+    h.add(Sphere((1.5, 0.6, 3.5), 0.6, MixedMaterial(Metal(C32(0.9, 0.5, 0.3)), Lambertian(C32(0.1, 0.2, 0.8)), 0.4)))
+    h.add(Sphere((-1.2, 0.5, 3.2), 0.5, None))
+    h.add(Sphere((0.0, 1.0, 0.0), 0.7, Lambertian(C32(0.7, 0.3, 0.1))).with_speed((0.0, 0.8, 0.0)))
+    h.add(Box((-5.0, 0.0, -3.0), (-4.0, 1.5, -2.0), Lambertian(C32(0.3, 0.6, 0.3))))
+    h.add(AARect.new_xz(AARectMetrics(2.5, (1.0, 4.0), (-3.0, 0.0)), DiffuseMetal(20.0, C32(0.8, 0.8, 0.2))))
+    cut = Intersection(Quadric(1.0, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 1.0, 0.0, -1.44, None),
+                       Box((-1.0, -1.0, -1.0), (1.0, 1.0, 1.0), None), Lambertian(C32(0.6, 0.2, 0.6)))
+    st = TransformStack()
+    st.push(Transform.rotate_by_y_axis(0.4))
+    st.push(Transform.translate((4.5, 1.0, -0.5)))
+    h.add(TfFacade(cut, st))
+    h.add(Difference(Box((-2.5, 0.0, -3.0), (-1.0, 1.4, -1.8), Lambertian(C32(0.8, 0.2, 0.2))),
+                     Sphere((-1.75, 1.4, -2.4), 0.6, None), None))
+    lights = HittableList()
+    lights.add(light)
+    cam = CameraBuilder().look_from(Point3(9.0, 3.0, 7.0)).look_at(Point3(0.0, 0.8, 0.0)).fov(40.0) \
+        .aperture(0.1).focus(11.0).shutter_speed(1.0).width(width).height(height).build()
+    return cam, World(h, lights, Gradient(C32(0.3, 0.4, 0.5), C32(0.7, 0.89, 1.0)), (0.0, cam.shutter_speed))

@@ -1,11 +1,11 @@
 #!/bin/bash
 # dev: VGPRs / scratch / occupancy of the kernels of one unit of rs_kernels.hip whose names match a pattern,
 # compiled with exactly the flags raysnail_amd/csrc/Makefile gives that unit (its unit-flags-<unit> target).
-# usage: tools/regs.sh <pattern> <unit: common | 0 .. 5> [extra hipcc flags ...]
+# usage: tools/regs.sh <pattern> <unit: common | 0 .. 6> [extra hipcc flags ...]
 # one line per kernel: VGPRs scratch-bytes waves/SIMD name
 set -eu
 R=$(cd "$(dirname "$0")/.." && pwd)
-[ $# -ge 2 ] || { echo "usage: $0 <pattern> <unit: common | 0 .. 5> [extra hipcc flags ...]" >&2; exit 2; }
+[ $# -ge 2 ] || { echo "usage: $0 <pattern> <unit: common | 0 .. 6> [extra hipcc flags ...]" >&2; exit 2; }
 pat=$1; unit=$2; shift 2
 HIPCC=${HIPCC:-/opt/rocm/bin/hipcc}
 flags=$(make -s --no-print-directory -C "$R/raysnail_amd/csrc" unit-flags-$unit)
