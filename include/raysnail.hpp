@@ -531,6 +531,17 @@ struct PixelController {  // src/painter.rs:34-38
     virtual bool calculate_pixel(size_t x, size_t y) const = 0;
 };
 
+// rs_denoise's knobs (the edge-avoiding a-trous filter over the feature frames, include/raysnail_hip.h); the defaults
+// are the header's
+struct DenoiseSettings {
+    uint32_t levels = RS_DENOISE_LEVELS;
+    float sigma_color = RS_DENOISE_SIGMA_COLOR, sigma_normal = RS_DENOISE_SIGMA_NORMAL, sigma_depth = RS_DENOISE_SIGMA_DEPTH;
+};
+// rs_denoise in place on a W x H frame (shot's, or render_passes' result), guided by shot_features' frames (either may
+// be null); gamma: the frame carries the sqrt gamma. Throws Error (RS_E_INVALID on a bad size or setting).
+void denoise(std::vector<Pixel>& pixels, const std::vector<Pixel>* albedo, const std::vector<Pixel>* normal, int W, int H,
+             const DenoiseSettings& settings = DenoiseSettings(), bool gamma = true);
+
 class TakePhotoSettings {  // src/camera.rs:103-154 + the GPU painter knobs (seed / pass / rows / mode)
 public:
     explicit TakePhotoSettings(const Camera& c) : camera_(c) {}
@@ -556,6 +567,11 @@ public:
     // (depth, gamma and mode do not apply) and pixel_map as the mask.
     struct Features { std::vector<Pixel> albedo, normal; };
     Features shot_features(World& world, const PixelController* pixel_map = nullptr);
+    // The photo and its feature frames (the same seed, pass, rows and mask), then denoise() with the photo's gamma.
+    // last_stats() is the beauty frame's.
+    struct Denoised { std::vector<Pixel> denoised, beauty; };
+    Denoised shot_denoised(World& world, const PixelController* pixel_map = nullptr,
+                           const DenoiseSettings& settings = DenoiseSettings());
     const rs_render_stats& last_stats() const { return stats_; }
 private:
     std::vector<uint8_t> mask_of(const PixelController* pixel_map) const;

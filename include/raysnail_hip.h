@@ -406,6 +406,63 @@ int rs_noise_map_device(const float* d_rgba, uint32_t width, uint32_t height, fl
 int rs_noise_map(const float* rgba, uint32_t width, uint32_t height, float threshold, uint8_t* redo,
                  rs_noise_stats* stats);
 
+/* ---- denoiser: a guided, edge-avoiding a-trous wavelet filter (Dammertz, Sewtz, Hanika, Lensch 2010; no reference
+ * counterpart) over a beauty frame and, optionally, the first-hit feature frames of rs_render_features ----
+ * Scene-free, like rs_noise_map: frames are W*H RGBA f32. beauty = an rs_render frame (alpha 1, masked pixels
+ * [0,0,0,0]); albedo = [r, g, b, coverage] or NULL (no demodulation); normal = [nx, ny, nz, depth] or NULL (no normal
+ * and depth weights). Defaults (RS_DENOISE_*): levels 5, sigma_color 0.3, sigma_normal 0.25, sigma_depth 0.1.
+ * RS_E_INVALID before anything touches the device: beauty, out (or d_work) NULL; levels outside 1 .. 8; a sigma that
+ * is not finite or outside [1e-4, 1e4]; gamma not 0 or 1; W H = 0 or > 0x7FFFFFFF.
+ *
+ * Arithmetic: all f32, every operation below rounded once (IEEE division and square root, denormals kept, no
+ * contraction), no transcendental function; a + b + c without brackets is never written. On the host, in f32:
+ *   ic_i = 1 / ((sigma_color 2^-i) (sigma_color 2^-i))   for level i (the colour sigma halves per level)
+ *   inv_n = 1 / (sigma_normal sigma_normal), inv_d = 1 / (sigma_depth sigma_depth)
+ * Prepare, per pixel p (B = beauty[p], Al = albedo[p], g_p = normal[p] exactly as the frame holds it: premultiplied by
+ * coverage, not renormalised):
+ *   c = B.rgb; gamma == 1: c = c c per channel (undoes into_color's sqrt)
+ *   albedo given: u = 1 - Al.w; a' = Al.rgb + u (the un-covered share counts as albedo 1: a sky pixel demodulates by
+ *                 1); m = max(a', 1e-3) per channel; c = c / m
+ *   usable(p) = B.a != 0 and B.rgb finite and (albedo given: Al's four channels finite) and (normal given: g_p's four
+ *               channels finite) and c's three channels finite
+ * Level i = 0 .. levels-1, step s = 2^i, from level i's colours c to level i+1's, for a usable p:
+ *   taps q = p + s (dx, dy), dy = -2 .. 2 the outer loop, dx = -2 .. 2 the inner; a tap outside the frame or on a pixel
+ *   that is not usable is skipped (it adds nothing, not even a zero); k = {1, 4, 6, 4, 1} / 16, h = k[dx] k[dy] (exact)
+ *   the tap q = p has weight w = h(0, 0) exactly; every other tap, with D_ = the tap's value minus p's:
+ *     dc2 = (D_r D_r + D_g D_g) + D_b D_b                  on level i's colours
+ *     A = 1 + dc2 ic_i
+ *     normal given:  dn2 = (D_x D_x + D_y D_y) + D_z D_z   on g.xyz;   dd = g_q.w - g_p.w
+ *                    M = max(max(|g_p.w|, |g_q.w|), 1e-6); M2 = M M    (depth is compared relatively: feature depths
+ *                    B = 1 + dn2 inv_n;  D = M2 + (dd dd) inv_d         are world distances)
+ *                    w = h (M2 / ((A B) D))
+ *     normal NULL:   w = h (1 / A)
+ *   (rational -- Cauchy -- edge-stopping kernels on squared differences: one division per tap)
+ *   S_c (three channels) and S_w start from +0.0 and add w c_q and w in tap order; the new colour is S_c / S_w
+ *   a pixel that is not usable keeps its value through the levels
+ * Finish: a usable p gets c m per channel (albedo given: the same m), then sqrt per channel if gamma == 1, and alpha
+ * B.a; a pixel that is not usable gets the four channels of B bit for bit (a NaN pixel stays that NaN pixel and
+ * reaches no neighbour; a masked pixel stays [0,0,0,0]).
+ * Ranges: a usable pixel's |depth| must stay below 2^63 (M2 overflows beyond) and colours below about 1e18, or
+ * infinities and NaNs appear in the sums as IEEE arithmetic gives them.
+ *
+ * rs_denoise_device: device pointers; enqueues one prepare launch and `levels` a-trous launches on `stream`
+ * (hipStream_t, NULL = default) of the current device, never synchronises and allocates nothing. d_work is caller
+ * memory of exactly 2 W H 4 floats (two colour planes; the guide is read in place). d_out may equal d_beauty (the
+ * last level reads d_work and the guides, and B only at its own pixel); it must not overlap d_work or the guides.
+ * rs_denoise: host buffers; uploads, runs the device variant on the default stream, synchronises, downloads (out may
+ * equal beauty). Additive extension of ABI 6. */
+#define RS_DENOISE_LEVELS       5
+#define RS_DENOISE_SIGMA_COLOR  (0.3f)
+#define RS_DENOISE_SIGMA_NORMAL (0.25f)
+#define RS_DENOISE_SIGMA_DEPTH  (0.1f)
+int rs_denoise_device(const float* d_beauty, const float* d_albedo, const float* d_normal,
+                      uint32_t width, uint32_t height, uint32_t levels,
+                      float sigma_color, float sigma_normal, float sigma_depth, int32_t gamma,
+                      float* d_out, float* d_work, void* stream);
+int rs_denoise(const float* beauty, const float* albedo, const float* normal,
+               uint32_t width, uint32_t height, uint32_t levels,
+               float sigma_color, float sigma_normal, float sigma_depth, int32_t gamma, float* out);
+
 /* ---- diagnostics (parity probes used by tests/) ---- */
 /* World::hit (world.rs:63-65) for n rays on the device. rays: n*7 doubles (origin, direction,
  * time); out: n*13 doubles = [hit, t1, t2, p.xyz, n.xyz, u, v, outside, material id] (u, v are

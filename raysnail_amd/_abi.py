@@ -52,6 +52,12 @@ RS_MODE_AUTO = 0
 RS_MODE_MEGAKERNEL = 1
 RS_MODE_WAVEFRONT = 2
 
+# rs_denoise's defaults (include/raysnail_hip.h RS_DENOISE_*)
+RS_DENOISE_LEVELS = 5
+RS_DENOISE_SIGMA_COLOR = 0.3
+RS_DENOISE_SIGMA_NORMAL = 0.25
+RS_DENOISE_SIGMA_DEPTH = 0.1
+
 
 class rs_texture_desc(C.Structure):
     _fields_ = [("kind", C.c_int32), ("data", C.c_int32), ("even", C.c_float * 4), ("odd", C.c_float * 4),
@@ -179,6 +185,12 @@ def load() -> C.CDLL:
     lib.rs_noise_map_device.restype = C.c_int
     lib.rs_noise_map.argtypes = [VP, C.c_uint32, C.c_uint32, C.c_float, VP, C.POINTER(rs_noise_stats)]
     lib.rs_noise_map.restype = C.c_int
+    lib.rs_denoise_device.argtypes = [VP, VP, VP, C.c_uint32, C.c_uint32, C.c_uint32, C.c_float, C.c_float, C.c_float,
+                                      C.c_int32, VP, VP, VP]
+    lib.rs_denoise_device.restype = C.c_int
+    lib.rs_denoise.argtypes = [VP, VP, VP, C.c_uint32, C.c_uint32, C.c_uint32, C.c_float, C.c_float, C.c_float,
+                               C.c_int32, VP]
+    lib.rs_denoise.restype = C.c_int
     lib.rs_probe_samples.argtypes = [VP, C.POINTER(rs_camera_desc), C.POINTER(rs_render_settings), C.c_uint32,
                                      C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p]
     lib.rs_probe_samples.restype = C.c_int
@@ -221,5 +233,6 @@ EXPORTED_SYMBOLS = [
     "rs_difference", "rs_transformed", "rs_constant_medium", "rs_world_add", "rs_lights_add", "rs_set_background", "rs_set_time_range",
     "rs_scene_commit", "rs_scene_commit_devices", "rs_scene_get_info", "rs_scene_set_lanes",
     "rs_scene_set_frames_in_flight", "rs_scene_set_workspace", "rs_render", "rs_render_rows", "rs_render_device", "rs_render_device_passes", "rs_render_features", "rs_render_features_device", "rs_combine_pixels_device", "rs_noise_map_device", "rs_noise_map",
+    "rs_denoise_device", "rs_denoise",
     "rs_probe_world_hit", "rs_probe_samples",
 ]

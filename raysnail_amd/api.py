@@ -669,6 +669,51 @@ class DeviceScene:
         return out
 
 
+# --------------------------------------------------------------------------- denoiser ----
+@dataclass
+class DenoiseSettings:
+    """rs_denoise's knobs; the defaults are the header's RS_DENOISE_* (include/raysnail_hip.h)."""
+    levels: int = A.RS_DENOISE_LEVELS
+    sigma_color: float = A.RS_DENOISE_SIGMA_COLOR
+    sigma_normal: float = A.RS_DENOISE_SIGMA_NORMAL
+    sigma_depth: float = A.RS_DENOISE_SIGMA_DEPTH
+
+
+def denoise(beauty: np.ndarray, albedo: Optional[np.ndarray] = None, normal: Optional[np.ndarray] = None,
+            settings: Optional[DenoiseSettings] = None, gamma: bool = True) -> np.ndarray:
+    """rs_denoise on (H, W, 4) float32 frames: the edge-avoiding a-trous filter of the beauty frame, guided by the
+    first-hit feature frames (render_features) where given. gamma: the beauty frame carries the sqrt gamma.
+    Returns a new frame."""
+    lib = A.load()
+    st = settings or DenoiseSettings()
+    beauty = np.ascontiguousarray(beauty, dtype=np.float32)
+    assert beauty.ndim == 3 and beauty.shape[2] == 4
+    H, W = beauty.shape[:2]
+    ptrs = []
+    for g in (albedo, normal):
+        if g is not None:
+            g = np.ascontiguousarray(g, dtype=np.float32)
+            assert g.shape == beauty.shape
+        ptrs.append(g)
+    out = np.empty_like(beauty)
+    _check(lib, lib.rs_denoise(beauty.ctypes.data, None if ptrs[0] is None else ptrs[0].ctypes.data,
+                               None if ptrs[1] is None else ptrs[1].ctypes.data, W, H, st.levels, st.sigma_color,
+                               st.sigma_normal, st.sigma_depth, int(bool(gamma)), out.ctypes.data), "rs_")
+    return out
+
+
+def denoise_device(d_beauty_ptr: int, d_albedo_ptr: int, d_normal_ptr: int, width: int, height: int, d_out_ptr: int,
+                   d_work_ptr: int, settings: Optional[DenoiseSettings] = None, gamma: bool = True,
+                   stream_ptr: int = 0) -> None:
+    """rs_denoise_device on device frames: enqueued on the stream, no synchronisation, no allocation. d_work_ptr:
+    2 * width * height * 4 floats of the caller's; the guide pointers may be 0; d_out_ptr may equal d_beauty_ptr."""
+    lib = A.load()
+    st = settings or DenoiseSettings()
+    _check(lib, lib.rs_denoise_device(d_beauty_ptr or None, d_albedo_ptr or None, d_normal_ptr or None, width, height,
+                                      st.levels, st.sigma_color, st.sigma_normal, st.sigma_depth, int(bool(gamma)),
+                                      d_out_ptr or None, d_work_ptr or None, stream_ptr or None), "rs_")
+
+
 # ----------------------------------------------------------------------------- camera ----
 class Camera:
     """src/camera.rs:18-91 (the basis itself is computed inside the library, camera.rs:37-73)."""
@@ -841,6 +886,16 @@ class TakePhotoSettings:
                              for y in range(cam.height)], dtype=np.uint8)
         albedo, normal, self.last_stats = world.device_scene().render_features(cam, self.settings(), mask)
         return albedo, normal
+
+    def shot_denoised(self, world: World, pixel_map: Optional[PixelController] = None,
+                      settings: Optional[DenoiseSettings] = None) -> Tuple[np.ndarray, np.ndarray]:
+        """The photo and its feature frames (the same seed, pass, rows and mask), then rs_denoise with the photo's
+        gamma: returns (denoised, beauty), (H, W, 4) float32 each. No reference counterpart."""
+        beauty = self.shot_to_target(None, world, None, None, pixel_map)
+        stats = self.last_stats
+        albedo, normal = self.shot_features(world, pixel_map)
+        self.last_stats = stats  # the beauty frame's
+        return denoise(beauty, albedo, normal, settings, self._gamma), beauty
 
     def shot(self, path, world: World) -> np.ndarray:
         """src/camera.rs:290-295 (path is ignored upstream too)."""

@@ -3179,6 +3179,62 @@ int rs_noise_map(const float* rgba, uint32_t width, uint32_t height, float thres
     });
 }
 
+// rs_denoise[_device]'s argument checks (everything but the buffers), before anything touches the device
+static void validate_denoise(uint32_t width, uint32_t height, uint32_t levels, float sigma_color, float sigma_normal,
+                             float sigma_depth, int32_t gamma) {
+    if (levels < 1 || levels > 8) throw Error(RS_E_INVALID, "denoise: levels outside 1 .. 8");
+    for (float sg : {sigma_color, sigma_normal, sigma_depth})
+        if (!(sg >= 1e-4f && sg <= 1e4f)) throw Error(RS_E_INVALID, "denoise: sigma not finite or outside [1e-4, 1e4]");
+    if (gamma != 0 && gamma != 1) throw Error(RS_E_INVALID, "denoise: gamma is not 0 or 1");
+    const uint64_t n = (uint64_t)width * height;
+    if (n == 0) throw Error(RS_E_INVALID, "denoise: empty frame");
+    if (n > 0x7FFFFFFFull) throw Error(RS_E_INVALID, "denoise: frame too large");
+}
+
+int rs_denoise_device(const float* d_beauty, const float* d_albedo, const float* d_normal, uint32_t width, uint32_t height,
+                      uint32_t levels, float sigma_color, float sigma_normal, float sigma_depth, int32_t gamma,
+                      float* d_out, float* d_work, void* stream) {
+    return run([&] {
+        validate_denoise(width, height, levels, sigma_color, sigma_normal, sigma_depth, gamma);
+        if (!d_beauty || !d_out || !d_work) throw Error(RS_E_INVALID, "denoise: null argument");
+        // the contract's constants, in f32 (the colour sigma halves per level: an exact scaling)
+        float ic[8];
+        float sc = sigma_color;
+        for (uint32_t i = 0; i < levels; ++i, sc = sc * 0.5f) ic[i] = 1.0f / (sc * sc);
+        const float inv_n = 1.0f / (sigma_normal * sigma_normal), inv_d = 1.0f / (sigma_depth * sigma_depth);
+        HIP_OK(launch_denoise(d_beauty, d_albedo, d_normal, width, height, levels, ic, inv_n, inv_d, gamma, d_out, d_work,
+                              (hipStream_t)stream));
+    });
+}
+
+int rs_denoise(const float* beauty, const float* albedo, const float* normal, uint32_t width, uint32_t height,
+               uint32_t levels, float sigma_color, float sigma_normal, float sigma_depth, int32_t gamma, float* out) {
+    return run([&] {
+        validate_denoise(width, height, levels, sigma_color, sigma_normal, sigma_depth, gamma);
+        if (!beauty || !out) throw Error(RS_E_INVALID, "denoise: null argument");
+        const size_t frame = (size_t)width * height * 4 * sizeof(float);
+        // one allocation: beauty (the output, in place), albedo, normal, the two work planes
+        float* d = nullptr;
+        HIP_OK(hipMalloc((void**)&d, 5 * frame));
+        float* d_beauty = d;
+        float* d_albedo = albedo ? d + frame / sizeof(float) : nullptr;
+        float* d_normal = normal ? d + 2 * (frame / sizeof(float)) : nullptr;
+        float* d_work = d + 3 * (frame / sizeof(float));
+        hipError_t e = hipMemcpy(d_beauty, beauty, frame, hipMemcpyHostToDevice);
+        if (e == hipSuccess && albedo) e = hipMemcpy(d_albedo, albedo, frame, hipMemcpyHostToDevice);
+        if (e == hipSuccess && normal) e = hipMemcpy(d_normal, normal, frame, hipMemcpyHostToDevice);
+        int rc = RS_OK;
+        if (e == hipSuccess)
+            rc = rs_denoise_device(d_beauty, d_albedo, d_normal, width, height, levels, sigma_color, sigma_normal,
+                                   sigma_depth, gamma, d_beauty, d_work, nullptr);
+        if (e == hipSuccess && rc == RS_OK) e = hipStreamSynchronize(nullptr);
+        if (e == hipSuccess && rc == RS_OK) e = hipMemcpy(out, d_beauty, frame, hipMemcpyDeviceToHost);
+        (void)hipFree(d);
+        HIP_OK(e);
+        if (rc != RS_OK) throw Error(rc, g_last_error);
+    });
+}
+
 int rs_probe_world_hit(rs_scene* s, const double* rays, uint32_t n, double tmin, double tmax, double* out) {
     return run([&] {
         S(s);

@@ -218,6 +218,12 @@ hipError_t launch_probe_hit(const SceneRef& s, const double* rays, uint32_t n, d
 // (RGBA f32; either may be null). seg_counter (may be null): += the world.hit calls. At most max_blocks blocks.
 hipError_t launch_features(const SceneRef& s, const DCamera& c, const PathParams& p, float* out_albedo, float* out_normal,
                            unsigned long long* seg_counter, int sm, uint32_t max_blocks, hipStream_t st);
+// The a-trous denoiser (rs_denoise.hip; contract in raysnail_hip.h): k_dn_prepare, then `levels` k_dn_atrous launches
+// ping-ponging between the two W H float4 halves of `work`, the last one finishing into `out` (which may be `beauty`).
+// albedo / normal may be null; ic[i] is level i's colour constant; width height <= 2^31 - 1 is the caller's check.
+hipError_t launch_denoise(const float* beauty, const float* albedo, const float* normal, uint32_t width, uint32_t height,
+                          uint32_t levels, const float* ic, float inv_n, float inv_d, int gamma, float* out, float* work,
+                          hipStream_t st);
 // acc[c * n_pix + pixel] += sum over the batch's samples in sample order (deterministic; item-major
 // radiance rad[3 * item + c], items sample-plane by sample-plane); the last batch writes into_color of the sum into the frame instead (k_finalize's
 // arithmetic, one launch less) and zeroes zero[0, n_zero) (the frame's queue counters) for the next

@@ -393,6 +393,31 @@ TakePhotoSettings::Features TakePhotoSettings::shot_features(World& world, const
     return f;
 }
 
+void denoise(std::vector<Pixel>& pixels, const std::vector<Pixel>* albedo, const std::vector<Pixel>* normal, int W, int H,
+             const DenoiseSettings& settings, bool gamma) {
+    if (W < 0 || H < 0) throw Error(RS_E_INVALID, "denoise: negative size");
+    const size_t npx = (size_t)W * (size_t)H;
+    if (pixels.size() != npx || (albedo && albedo->size() != npx) || (normal && normal->size() != npx))
+        throw Error(RS_E_INVALID, "denoise: frame size mismatch");
+    float* px = reinterpret_cast<float*>(pixels.data());
+    check_rs(rs_denoise(px, albedo ? reinterpret_cast<const float*>(albedo->data()) : nullptr,
+                        normal ? reinterpret_cast<const float*>(normal->data()) : nullptr, (uint32_t)W, (uint32_t)H,
+                        settings.levels, settings.sigma_color, settings.sigma_normal, settings.sigma_depth, gamma ? 1 : 0,
+                        px));
+}
+
+TakePhotoSettings::Denoised TakePhotoSettings::shot_denoised(World& world, const PixelController* pixel_map,
+                                                             const DenoiseSettings& settings) {
+    Denoised d;
+    d.beauty = shot_to_target(nullptr, world, nullptr, nullptr, pixel_map);
+    const rs_render_stats beauty_stats = stats_;
+    const Features f = shot_features(world, pixel_map);
+    stats_ = beauty_stats;
+    d.denoised = d.beauty;
+    denoise(d.denoised, &f.albedo, &f.normal, (int)camera_.desc().width, (int)camera_.desc().height, settings, gamma_);
+    return d;
+}
+
 std::vector<Pixel> TakePhotoSettings::shot_to_target(const char*, World& world, PainterTarget* target,
                                                      PainterController*, const PixelController* pixel_map) {
     const rs_camera_desc& cam = camera_.desc();
