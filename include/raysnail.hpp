@@ -542,6 +542,23 @@ struct DenoiseSettings {
 void denoise(std::vector<Pixel>& pixels, const std::vector<Pixel>* albedo, const std::vector<Pixel>* normal, int W, int H,
              const DenoiseSettings& settings = DenoiseSettings(), bool gamma = true);
 
+// rs_pass_moments over K >= 1 pass frames of W x H pixels (independent renders of the same pixels): the per-pixel
+// mean, a frame in shot's convention, and var = [var_r, var_g, var_b, n], the variance of that mean in linear
+// radiance over the n frames that contribute to the pixel. gamma: the frames carry the sqrt gamma.
+struct PassMoments { std::vector<Pixel> mean, var; };
+PassMoments pass_moments(const std::vector<std::vector<Pixel>>& frames, int W, int H, bool gamma = true);
+// rs_denoise_var's knobs (denoise's filter with the colour weight normalised by the local variance); the defaults are
+// the header's
+struct DenoiseVarSettings {
+    uint32_t levels = RS_DENOISE_VAR_LEVELS;
+    float k_color = RS_DENOISE_VAR_K_COLOR, sigma_normal = RS_DENOISE_SIGMA_NORMAL, sigma_depth = RS_DENOISE_SIGMA_DEPTH;
+};
+// rs_denoise_var in place on a W x H frame and its variance frame (pass_moments' pair), guided as denoise; out_var
+// (may be null) receives the filtered variance frame. Throws Error (RS_E_INVALID on a bad size or setting).
+void denoise_var(std::vector<Pixel>& pixels, const std::vector<Pixel>& var, const std::vector<Pixel>* albedo,
+                 const std::vector<Pixel>* normal, int W, int H, const DenoiseVarSettings& settings = DenoiseVarSettings(),
+                 bool gamma = true, std::vector<Pixel>* out_var = nullptr);
+
 class TakePhotoSettings {  // src/camera.rs:103-154 + the GPU painter knobs (seed / pass / rows / mode)
 public:
     explicit TakePhotoSettings(const Camera& c) : camera_(c) {}
@@ -572,6 +589,12 @@ public:
     struct Denoised { std::vector<Pixel> denoised, beauty; };
     Denoised shot_denoised(World& world, const PixelController* pixel_map = nullptr,
                            const DenoiseSettings& settings = DenoiseSettings());
+    // `passes` (>= 2, or Error RS_E_INVALID) progressive passes of the photo -- pass indices pass_index ..
+    // pass_index + passes - 1, `samples` each, every frame what shot gives for that pass -- and the first pass's
+    // feature frames; then pass_moments() and denoise_var() with the photo's gamma. last_stats() is the last pass's.
+    struct DenoisedPasses { std::vector<Pixel> denoised, mean, var; };
+    DenoisedPasses shot_denoised_passes(World& world, size_t passes, const PixelController* pixel_map = nullptr,
+                                        const DenoiseVarSettings& settings = DenoiseVarSettings());
     const rs_render_stats& last_stats() const { return stats_; }
 private:
     std::vector<uint8_t> mask_of(const PixelController* pixel_map) const;

@@ -463,6 +463,90 @@ int rs_denoise(const float* beauty, const float* albedo, const float* normal,
                uint32_t width, uint32_t height, uint32_t levels,
                float sigma_color, float sigma_normal, float sigma_depth, int32_t gamma, float* out);
 
+/* ---- pass moments: per-pixel mean, and variance of that mean, over K pass frames (no reference counterpart) ----
+ * Scene-free. The K frames are independent renders of the same pixels (rs_render_device_passes' frames: W*H RGBA f32,
+ * alpha 1, masked pixels [0,0,0,0]); their spread estimates the noise of their mean, which rs_denoise_var consumes.
+ * RS_E_INVALID before anything touches the device: frames NULL or a NULL frame pointer; n_frames outside 1 .. 64;
+ * gamma not 0 or 1; W H = 0 or > 0x7FFFFFFF; mean and var both NULL (either alone may be NULL: not written).
+ *
+ * Arithmetic: all f32, every operation rounded once (IEEE division and square root, denormals kept, no contraction),
+ * no transcendental function. Per pixel p, with F_k = frame k's pixel p, k = 0 .. n_frames-1 in that order:
+ *   frame k contributes when F_k.a != 0 and F_k.rgb are finite (rs_denoise's masked and NaN conventions)
+ *   x_k = F_k.rgb; gamma == 1: x_k = x_k x_k per channel (undoes into_color's sqrt: moments of linear radiance)
+ *   n = the number of contributing frames
+ *   S = the sum of x_k over the contributing k in frame order, from +0.0;   mu = S / (float)n
+ *   Q = the sum of (x_k - mu)(x_k - mu) over the contributing k in the same order, from +0.0 (the difference rounded,
+ *       then its square, then the addition)
+ *   v = Q / ((float)n (float)(n - 1)) for n >= 2 (the product of the two is exact), else +0.0
+ *   mean[p] = [mu (gamma == 1: sqrt(mu) per channel), 1.0] for n >= 1, [0,0,0,0] for n = 0: a frame in rs_render's
+ *             convention
+ *   var[p]  = [v_r, v_g, v_b, (float)n]: linear radiance, the variance of the mean (not of one pass), never gamma
+ * A contributing x_k x_k that overflows gives the infinities and NaNs IEEE arithmetic gives.
+ *
+ * rs_pass_moments_device: d_frames is a HOST array of n_frames device pointers; they travel in the kernel's argument
+ * block (no device-side table, no copy). One launch on `stream` (hipStream_t, NULL = default) of the current device,
+ * never synchronises, allocates nothing. A thread reads its pixel of every frame, twice, before it writes that pixel:
+ * d_mean may alias any input frame. d_var must not overlap the frames or d_mean.
+ * rs_pass_moments: host buffers; uploads, runs the device variant on the default stream, synchronises, downloads
+ * (mean may be one of the frames). Additive extension of ABI 6. */
+int rs_pass_moments_device(const float* const* d_frames, uint32_t n_frames, uint32_t width, uint32_t height,
+                           int32_t gamma, float* d_mean, float* d_var, void* stream);
+int rs_pass_moments(const float* const* frames, uint32_t n_frames, uint32_t width, uint32_t height,
+                    int32_t gamma, float* mean, float* var);
+
+/* ---- variance-guided denoiser: rs_denoise's a-trous filter with the colour edge-stopping weight normalised by a
+ * per-pixel variance that is itself filtered level by level (Schied et al. 2017, SVGF's spatial filter without its
+ * temporal half; no reference counterpart) ----
+ * Frames as rs_denoise's, plus var = rs_pass_moments' variance frame [var_r, var_g, var_b, n] of the beauty frame
+ * (linear radiance). Everything not restated here is rs_denoise's contract unchanged: the arithmetic rules, the tap
+ * order (dy outer, dx inner), k and h, dn2, dd, M, M2, B, D, skipped taps, the finish of the colour, the pass-through
+ * of pixels that are not usable, the ranges. k_color (RS_DENOISE_VAR_K_COLOR) replaces sigma_color and takes a sigma's
+ * range. Defaults (RS_DENOISE_VAR_*): levels 5, k_color 2.5; sigma_normal and sigma_depth default to RS_DENOISE_SIGMA_*.
+ * RS_E_INVALID before anything touches the device: beauty, var, out (or d_work) NULL; levels outside 1 .. 8; k_color
+ * or a sigma not finite or outside [1e-4, 1e4]; gamma not 0 or 1; W H = 0 or > 0x7FFFFFFF.
+ *
+ * On the host, in f32: inv_n, inv_d as rs_denoise's. The colour constant does not halve per level: the variance shrinks.
+ * Prepare, per pixel p (V = var[p]): c, m as rs_denoise's, and
+ *   mm = m m per channel (albedo given; rounded once); v = V.rgb / mm (albedo given), v = V.rgb (albedo NULL)
+ *   usable(p) = rs_denoise's usable(p) and V.rgb finite and >= 0 (-0.0 passes) and v's three channels finite
+ *   (V.w is not read before the finish)
+ * Level i = 0 .. levels-1, step s = 2^i, from level i's (c, v) to level i+1's, for a usable p:
+ *   t_q = (v_q.r + v_q.g) + v_q.b of level i's variances
+ *   vs_p: the 3 x 3 Gaussian-weighted mean of t around p at pixel spacing 1 (at every level): taps q = p + (dx, dy),
+ *         dy = -1 .. 1 the outer loop, dx = -1 .. 1 the inner, the centre in its place in that order; g = {1, 2, 1} / 4,
+ *         weight g[dx] g[dy] (exact); a tap outside the frame or on a pixel that is not usable is skipped;
+ *         N = the sum of (g[dx] g[dy]) t_q and G = the sum of g[dx] g[dy], both from +0.0 (product, then addition);
+ *         vs_p = N / G
+ *   iv = 1 / (k_color vs_p + RS_DENOISE_VAR_EPS)   (one division per pixel and level; EPS = 1e-6f keeps a
+ *        variance-free neighbourhood finite: there the filter degenerates to rs_denoise's with sigma_color 1e-3)
+ *   the 5 x 5 taps q = p + s (dx, dy) as rs_denoise's, with A = 1 + dc2 iv for every tap but the centre; B, D, M2, w as
+ *   there (normal NULL: w = h (1 / A)); the centre has w = h(0, 0)
+ *   S_c, S_w as rs_denoise's; S_v (three channels, from +0.0) adds ww v_q per channel in tap order, ww = w w
+ *   rounded once (the centre adds (h(0,0) h(0,0)) v_p)
+ *   new colour S_c / S_w; SS = S_w S_w (rounded once); new variance S_v / SS per channel
+ *   a pixel that is not usable takes no part and its plane values are never read
+ * Finish (with the last level): the colour as rs_denoise's. out_var[p], when given, = [v mm per channel (albedo
+ * given; the same mm) or v (albedo NULL), V.w] for a usable p, and V's four channels bit for bit otherwise.
+ *
+ * rs_denoise_var_device: device pointers; one prepare launch and `levels` a-trous launches on `stream` of the current
+ * device, never synchronises, allocates nothing. d_work is caller memory of exactly 4 W H 4 floats (two colour and two
+ * variance planes that ping-pong; the guide is read in place). d_out may equal d_beauty and d_out_var may equal d_var
+ * (the last level reads B and V only at its own pixel); neither may overlap d_work, the guides, or the other's input.
+ * d_out_var may be NULL.
+ * rs_denoise_var: host buffers (out may equal beauty, out_var may equal var or be NULL); uploads, runs the device
+ * variant on the default stream, synchronises, downloads. Additive extension of ABI 6. */
+#define RS_DENOISE_VAR_LEVELS   ((uint32_t)5)
+#define RS_DENOISE_VAR_K_COLOR  ((float)2.5)
+#define RS_DENOISE_VAR_EPS      ((float)1e-6)
+int rs_denoise_var_device(const float* d_beauty, const float* d_var, const float* d_albedo, const float* d_normal,
+                          uint32_t width, uint32_t height, uint32_t levels,
+                          float k_color, float sigma_normal, float sigma_depth, int32_t gamma,
+                          float* d_out, float* d_out_var, float* d_work, void* stream);
+int rs_denoise_var(const float* beauty, const float* var, const float* albedo, const float* normal,
+                   uint32_t width, uint32_t height, uint32_t levels,
+                   float k_color, float sigma_normal, float sigma_depth, int32_t gamma,
+                   float* out, float* out_var);
+
 /* ---- diagnostics (parity probes used by tests/) ---- */
 /* World::hit (world.rs:63-65) for n rays on the device. rays: n*7 doubles (origin, direction,
  * time); out: n*13 doubles = [hit, t1, t2, p.xyz, n.xyz, u, v, outside, material id] (u, v are

@@ -7,9 +7,10 @@ ABI (api.py) plus the scene builders for the benchmark configurations (scenes.py
 """
 from . import _abi  # noqa: F401
 from .api import (AARect, AARectMetrics, Box, Camera, CameraBuilder, Checker, Color, CommonMaterialSettings,  # noqa: F401
-                  DenoiseSettings, Dielectric, Difference, DiffuseLight, DiffuseMetal, Glass, Gradient, HittableList, Intersection,
+                  DenoiseSettings, DenoiseVarSettings, Dielectric, Difference, DiffuseLight, DiffuseMetal, Glass, Gradient, HittableList, Intersection,
                   Lambertian, MixedMaterial, Metal, PainterController, PainterTarget, PixelController, Point3,
                   Quadric, RaysnailError, Sphere, TakePhotoSettings, TfFacade, Transform, TransformStack,
-                  TriangleMesh, Vec3, World, denoise, denoise_device, realize)
+                  TriangleMesh, Vec3, World, denoise, denoise_device, denoise_var, denoise_var_device, pass_moments,
+                  pass_moments_device, realize)
 
 __all__ = [n for n in dir() if not n.startswith("_")]

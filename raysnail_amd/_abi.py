@@ -57,6 +57,10 @@ RS_DENOISE_LEVELS = 5
 RS_DENOISE_SIGMA_COLOR = 0.3
 RS_DENOISE_SIGMA_NORMAL = 0.25
 RS_DENOISE_SIGMA_DEPTH = 0.1
+# rs_denoise_var's (RS_DENOISE_VAR_*)
+RS_DENOISE_VAR_LEVELS = 5
+RS_DENOISE_VAR_K_COLOR = 2.5
+RS_DENOISE_VAR_EPS = 1e-6
 
 
 class rs_texture_desc(C.Structure):
@@ -191,6 +195,16 @@ def load() -> C.CDLL:
     lib.rs_denoise.argtypes = [VP, VP, VP, C.c_uint32, C.c_uint32, C.c_uint32, C.c_float, C.c_float, C.c_float,
                                C.c_int32, VP]
     lib.rs_denoise.restype = C.c_int
+    lib.rs_pass_moments_device.argtypes = [C.POINTER(VP), C.c_uint32, C.c_uint32, C.c_uint32, C.c_int32, VP, VP, VP]
+    lib.rs_pass_moments_device.restype = C.c_int
+    lib.rs_pass_moments.argtypes = [C.POINTER(VP), C.c_uint32, C.c_uint32, C.c_uint32, C.c_int32, VP, VP]
+    lib.rs_pass_moments.restype = C.c_int
+    lib.rs_denoise_var_device.argtypes = [VP, VP, VP, VP, C.c_uint32, C.c_uint32, C.c_uint32, C.c_float, C.c_float,
+                                          C.c_float, C.c_int32, VP, VP, VP, VP]
+    lib.rs_denoise_var_device.restype = C.c_int
+    lib.rs_denoise_var.argtypes = [VP, VP, VP, VP, C.c_uint32, C.c_uint32, C.c_uint32, C.c_float, C.c_float, C.c_float,
+                                   C.c_int32, VP, VP]
+    lib.rs_denoise_var.restype = C.c_int
     lib.rs_probe_samples.argtypes = [VP, C.POINTER(rs_camera_desc), C.POINTER(rs_render_settings), C.c_uint32,
                                      C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p]
     lib.rs_probe_samples.restype = C.c_int
@@ -234,5 +248,6 @@ EXPORTED_SYMBOLS = [
     "rs_scene_commit", "rs_scene_commit_devices", "rs_scene_get_info", "rs_scene_set_lanes",
     "rs_scene_set_frames_in_flight", "rs_scene_set_workspace", "rs_render", "rs_render_rows", "rs_render_device", "rs_render_device_passes", "rs_render_features", "rs_render_features_device", "rs_combine_pixels_device", "rs_noise_map_device", "rs_noise_map",
     "rs_denoise_device", "rs_denoise",
+    "rs_pass_moments_device", "rs_pass_moments", "rs_denoise_var_device", "rs_denoise_var",
     "rs_probe_world_hit", "rs_probe_samples",
 ]

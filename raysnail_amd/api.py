@@ -714,6 +714,87 @@ def denoise_device(d_beauty_ptr: int, d_albedo_ptr: int, d_normal_ptr: int, widt
                                       d_out_ptr or None, d_work_ptr or None, stream_ptr or None), "rs_")
 
 
+# ------------------------------------------------- pass moments, variance-guided denoiser ----
+def pass_moments(frames: Sequence[np.ndarray], gamma: bool = True) -> Tuple[np.ndarray, np.ndarray]:
+    """rs_pass_moments on K (H, W, 4) float32 pass frames (independent renders of the same pixels): returns (mean,
+    var) -- the per-pixel mean as a frame in render's convention, and var = [var_r, var_g, var_b, n], the variance
+    of that mean in linear radiance over the n frames that contribute to the pixel. gamma: the frames carry the sqrt
+    gamma."""
+    lib = A.load()
+    frames = [np.ascontiguousarray(f, dtype=np.float32) for f in frames]
+    if not frames:
+        raise RaysnailError(A.RS_E_INVALID, "pass_moments: n_frames outside 1 .. 64")
+    assert all(f.ndim == 3 and f.shape == frames[0].shape and f.shape[2] == 4 for f in frames)
+    H, W = frames[0].shape[:2]
+    ptrs = (C.c_void_p * len(frames))(*[C.c_void_p(f.ctypes.data) for f in frames])
+    mean, var = np.empty_like(frames[0]), np.empty_like(frames[0])
+    _check(lib, lib.rs_pass_moments(ptrs, len(frames), W, H, int(bool(gamma)), mean.ctypes.data, var.ctypes.data), "rs_")
+    return mean, var
+
+
+def pass_moments_device(d_frame_ptrs: Sequence[int], width: int, height: int, d_mean_ptr: int, d_var_ptr: int,
+                        gamma: bool = True, stream_ptr: int = 0) -> None:
+    """rs_pass_moments_device on device frames: one launch enqueued on the stream, no synchronisation, no allocation.
+    Either output pointer may be 0 (not both); d_mean_ptr may be one of the frames."""
+    lib = A.load()
+    n = len(d_frame_ptrs)
+    ptrs = (C.c_void_p * max(1, n))(*[C.c_void_p(p or None) for p in d_frame_ptrs])
+    _check(lib, lib.rs_pass_moments_device(ptrs, n, width, height, int(bool(gamma)), d_mean_ptr or None,
+                                           d_var_ptr or None, stream_ptr or None), "rs_")
+
+
+@dataclass
+class DenoiseVarSettings:
+    """rs_denoise_var's knobs; the defaults are the header's RS_DENOISE_VAR_* and RS_DENOISE_SIGMA_*."""
+    levels: int = A.RS_DENOISE_VAR_LEVELS
+    k_color: float = A.RS_DENOISE_VAR_K_COLOR
+    sigma_normal: float = A.RS_DENOISE_SIGMA_NORMAL
+    sigma_depth: float = A.RS_DENOISE_SIGMA_DEPTH
+
+
+def denoise_var(beauty: np.ndarray, var: np.ndarray, albedo: Optional[np.ndarray] = None,
+                normal: Optional[np.ndarray] = None, settings: Optional[DenoiseVarSettings] = None, gamma: bool = True,
+                want_var: bool = False):
+    """rs_denoise_var on (H, W, 4) float32 frames: denoise's a-trous filter with the colour weight normalised by the
+    local variance (var: pass_moments' variance frame of the beauty frame), the variance filtered along. Returns a
+    new frame, or with want_var the pair (frame, filtered variance frame)."""
+    lib = A.load()
+    st = settings or DenoiseVarSettings()
+    beauty = np.ascontiguousarray(beauty, dtype=np.float32)
+    assert beauty.ndim == 3 and beauty.shape[2] == 4
+    H, W = beauty.shape[:2]
+    var = np.ascontiguousarray(var, dtype=np.float32)
+    assert var.shape == beauty.shape
+    ptrs = []
+    for g in (albedo, normal):
+        if g is not None:
+            g = np.ascontiguousarray(g, dtype=np.float32)
+            assert g.shape == beauty.shape
+        ptrs.append(g)
+    out = np.empty_like(beauty)
+    out_var = np.empty_like(beauty) if want_var else None
+    _check(lib, lib.rs_denoise_var(beauty.ctypes.data, var.ctypes.data,
+                                   None if ptrs[0] is None else ptrs[0].ctypes.data,
+                                   None if ptrs[1] is None else ptrs[1].ctypes.data, W, H, st.levels, st.k_color,
+                                   st.sigma_normal, st.sigma_depth, int(bool(gamma)), out.ctypes.data,
+                                   None if out_var is None else out_var.ctypes.data), "rs_")
+    return (out, out_var) if want_var else out
+
+
+def denoise_var_device(d_beauty_ptr: int, d_var_ptr: int, d_albedo_ptr: int, d_normal_ptr: int, width: int, height: int,
+                       d_out_ptr: int, d_out_var_ptr: int, d_work_ptr: int,
+                       settings: Optional[DenoiseVarSettings] = None, gamma: bool = True, stream_ptr: int = 0) -> None:
+    """rs_denoise_var_device on device frames: enqueued on the stream, no synchronisation, no allocation. d_work_ptr:
+    4 * width * height * 4 floats of the caller's; the guide pointers and d_out_var_ptr may be 0; d_out_ptr may equal
+    d_beauty_ptr and d_out_var_ptr may equal d_var_ptr."""
+    lib = A.load()
+    st = settings or DenoiseVarSettings()
+    _check(lib, lib.rs_denoise_var_device(d_beauty_ptr or None, d_var_ptr or None, d_albedo_ptr or None,
+                                          d_normal_ptr or None, width, height, st.levels, st.k_color, st.sigma_normal,
+                                          st.sigma_depth, int(bool(gamma)), d_out_ptr or None, d_out_var_ptr or None,
+                                          d_work_ptr or None, stream_ptr or None), "rs_")
+
+
 # ----------------------------------------------------------------------------- camera ----
 class Camera:
     """src/camera.rs:18-91 (the basis itself is computed inside the library, camera.rs:37-73)."""
@@ -896,6 +977,29 @@ class TakePhotoSettings:
         albedo, normal = self.shot_features(world, pixel_map)
         self.last_stats = stats  # the beauty frame's
         return denoise(beauty, albedo, normal, settings, self._gamma), beauty
+
+    def shot_denoised_passes(self, world: World, passes: int, pixel_map: Optional[PixelController] = None,
+                             settings: Optional[DenoiseVarSettings] = None
+                             ) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+        """`passes` (>= 2) progressive passes of the photo -- pass indices pass_index .. pass_index + passes - 1,
+        `samples` each, every frame what shot gives for that pass -- and the first pass's feature frames (the same
+        seed, rows and mask); then pass_moments and denoise_var with the photo's gamma: returns (denoised, mean, var),
+        (H, W, 4) float32 each. last_stats is the last pass's. No reference counterpart."""
+        if passes < 2:
+            raise RaysnailError(A.RS_E_INVALID, "shot_denoised_passes: fewer than 2 passes")
+        first = self._pass
+        frames = []
+        try:
+            for k in range(passes):
+                self._pass = first + k
+                frames.append(self.shot_to_target(None, world, None, None, pixel_map))
+        finally:
+            self._pass = first
+        stats = self.last_stats
+        albedo, normal = self.shot_features(world, pixel_map)
+        self.last_stats = stats
+        mean, var = pass_moments(frames, self._gamma)
+        return denoise_var(mean, var, albedo, normal, settings, self._gamma), mean, var
 
     def shot(self, path, world: World) -> np.ndarray:
         """src/camera.rs:290-295 (path is ignored upstream too)."""

@@ -3235,6 +3235,99 @@ int rs_denoise(const float* beauty, const float* albedo, const float* normal, ui
     });
 }
 
+// rs_pass_moments[_device]'s argument checks, before anything touches the device
+static void validate_pass_moments(const float* const* frames, uint32_t n_frames, uint32_t width, uint32_t height,
+                                  int32_t gamma, const float* mean, const float* var) {
+    if (n_frames < 1 || n_frames > 64) throw Error(RS_E_INVALID, "pass_moments: n_frames outside 1 .. 64");
+    if (gamma != 0 && gamma != 1) throw Error(RS_E_INVALID, "pass_moments: gamma is not 0 or 1");
+    const uint64_t n = (uint64_t)width * height;
+    if (n == 0) throw Error(RS_E_INVALID, "pass_moments: empty frame");
+    if (n > 0x7FFFFFFFull) throw Error(RS_E_INVALID, "pass_moments: frame too large");
+    if (!frames) throw Error(RS_E_INVALID, "pass_moments: null argument");
+    for (uint32_t k = 0; k < n_frames; ++k)
+        if (!frames[k]) throw Error(RS_E_INVALID, "pass_moments: null frame pointer");
+    if (!mean && !var) throw Error(RS_E_INVALID, "pass_moments: null argument (both outputs)");
+}
+
+int rs_pass_moments_device(const float* const* d_frames, uint32_t n_frames, uint32_t width, uint32_t height, int32_t gamma,
+                           float* d_mean, float* d_var, void* stream) {
+    return run([&] {
+        validate_pass_moments(d_frames, n_frames, width, height, gamma, d_mean, d_var);
+        HIP_OK(launch_pass_moments(d_frames, n_frames, width * height, gamma, d_mean, d_var, (hipStream_t)stream));
+    });
+}
+
+int rs_pass_moments(const float* const* frames, uint32_t n_frames, uint32_t width, uint32_t height, int32_t gamma,
+                    float* mean, float* var) {
+    return run([&] {
+        validate_pass_moments(frames, n_frames, width, height, gamma, mean, var);
+        const size_t frame = (size_t)width * height * 4 * sizeof(float), fl = frame / sizeof(float);
+        // one allocation: the frames, then the mean and the variance
+        float* d = nullptr;
+        HIP_OK(hipMalloc((void**)&d, ((size_t)n_frames + 2) * frame));
+        const float* d_frames[64];
+        hipError_t e = hipSuccess;
+        for (uint32_t k = 0; k < n_frames && e == hipSuccess; ++k) {
+            d_frames[k] = d + k * fl;
+            e = hipMemcpy(d + k * fl, frames[k], frame, hipMemcpyHostToDevice);
+        }
+        float* d_mean = mean ? d + (size_t)n_frames * fl : nullptr;
+        float* d_var = var ? d + ((size_t)n_frames + 1) * fl : nullptr;
+        int rc = RS_OK;
+        if (e == hipSuccess) rc = rs_pass_moments_device(d_frames, n_frames, width, height, gamma, d_mean, d_var, nullptr);
+        if (e == hipSuccess && rc == RS_OK) e = hipStreamSynchronize(nullptr);
+        if (e == hipSuccess && rc == RS_OK && mean) e = hipMemcpy(mean, d_mean, frame, hipMemcpyDeviceToHost);
+        if (e == hipSuccess && rc == RS_OK && var) e = hipMemcpy(var, d_var, frame, hipMemcpyDeviceToHost);
+        (void)hipFree(d);
+        HIP_OK(e);
+        if (rc != RS_OK) throw Error(rc, g_last_error);
+    });
+}
+
+int rs_denoise_var_device(const float* d_beauty, const float* d_var, const float* d_albedo, const float* d_normal,
+                          uint32_t width, uint32_t height, uint32_t levels, float k_color, float sigma_normal,
+                          float sigma_depth, int32_t gamma, float* d_out, float* d_out_var, float* d_work, void* stream) {
+    return run([&] {
+        validate_denoise(width, height, levels, k_color, sigma_normal, sigma_depth, gamma);
+        if (!d_beauty || !d_var || !d_out || !d_work) throw Error(RS_E_INVALID, "denoise: null argument");
+        const float inv_n = 1.0f / (sigma_normal * sigma_normal), inv_d = 1.0f / (sigma_depth * sigma_depth);
+        HIP_OK(launch_denoise_var(d_beauty, d_var, d_albedo, d_normal, width, height, levels, k_color, inv_n, inv_d, gamma,
+                                  d_out, d_out_var, d_work, (hipStream_t)stream));
+    });
+}
+
+int rs_denoise_var(const float* beauty, const float* var, const float* albedo, const float* normal, uint32_t width,
+                   uint32_t height, uint32_t levels, float k_color, float sigma_normal, float sigma_depth, int32_t gamma,
+                   float* out, float* out_var) {
+    return run([&] {
+        validate_denoise(width, height, levels, k_color, sigma_normal, sigma_depth, gamma);
+        if (!beauty || !var || !out) throw Error(RS_E_INVALID, "denoise: null argument");
+        const size_t frame = (size_t)width * height * 4 * sizeof(float), fl = frame / sizeof(float);
+        // one allocation: beauty and var (the outputs, in place), albedo, normal, the four work planes
+        float* d = nullptr;
+        HIP_OK(hipMalloc((void**)&d, 8 * frame));
+        float* d_beauty = d;
+        float* d_var = d + fl;
+        float* d_albedo = albedo ? d + 2 * fl : nullptr;
+        float* d_normal = normal ? d + 3 * fl : nullptr;
+        float* d_work = d + 4 * fl;
+        hipError_t e = hipMemcpy(d_beauty, beauty, frame, hipMemcpyHostToDevice);
+        if (e == hipSuccess) e = hipMemcpy(d_var, var, frame, hipMemcpyHostToDevice);
+        if (e == hipSuccess && albedo) e = hipMemcpy(d_albedo, albedo, frame, hipMemcpyHostToDevice);
+        if (e == hipSuccess && normal) e = hipMemcpy(d_normal, normal, frame, hipMemcpyHostToDevice);
+        int rc = RS_OK;
+        if (e == hipSuccess)
+            rc = rs_denoise_var_device(d_beauty, d_var, d_albedo, d_normal, width, height, levels, k_color, sigma_normal,
+                                       sigma_depth, gamma, d_beauty, out_var ? d_var : nullptr, d_work, nullptr);
+        if (e == hipSuccess && rc == RS_OK) e = hipStreamSynchronize(nullptr);
+        if (e == hipSuccess && rc == RS_OK) e = hipMemcpy(out, d_beauty, frame, hipMemcpyDeviceToHost);
+        if (e == hipSuccess && rc == RS_OK && out_var) e = hipMemcpy(out_var, d_var, frame, hipMemcpyDeviceToHost);
+        (void)hipFree(d);
+        HIP_OK(e);
+        if (rc != RS_OK) throw Error(rc, g_last_error);
+    });
+}
+
 int rs_probe_world_hit(rs_scene* s, const double* rays, uint32_t n, double tmin, double tmax, double* out) {
     return run([&] {
         S(s);

@@ -224,6 +224,17 @@ hipError_t launch_features(const SceneRef& s, const DCamera& c, const PathParams
 hipError_t launch_denoise(const float* beauty, const float* albedo, const float* normal, uint32_t width, uint32_t height,
                           uint32_t levels, const float* ic, float inv_n, float inv_d, int gamma, float* out, float* work,
                           hipStream_t st);
+// Pass moments and the variance-guided a-trous denoiser (rs_denoise_var.hip; contracts in raysnail_hip.h).
+// launch_pass_moments: one k_pass_moments launch; the n_frames (1 .. 64) device pointers of the host array `frames`
+// travel in the kernel's argument block; mean / var: either may be null.
+// launch_denoise_var: k_dv_prepare, then `levels` k_dv_atrous launches ping-ponging between the two (colour, variance)
+// plane pairs of `work` (4 W H float4s: colour 0, colour 1, variance 0, variance 1), the last one finishing into `out`
+// (which may be `beauty`) and `out_var` (null, or possibly `var`). width height <= 2^31 - 1 is the caller's check.
+hipError_t launch_pass_moments(const float* const* frames, uint32_t n_frames, uint32_t n_pix, int gamma, float* mean,
+                               float* var, hipStream_t st);
+hipError_t launch_denoise_var(const float* beauty, const float* var, const float* albedo, const float* normal,
+                              uint32_t width, uint32_t height, uint32_t levels, float k_color, float inv_n, float inv_d,
+                              int gamma, float* out, float* out_var, float* work, hipStream_t st);
 // acc[c * n_pix + pixel] += sum over the batch's samples in sample order (deterministic; item-major
 // radiance rad[3 * item + c], items sample-plane by sample-plane); the last batch writes into_color of the sum into the frame instead (k_finalize's
 // arithmetic, one launch less) and zeroes zero[0, n_zero) (the frame's queue counters) for the next

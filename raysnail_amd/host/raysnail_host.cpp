@@ -418,6 +418,68 @@ TakePhotoSettings::Denoised TakePhotoSettings::shot_denoised(World& world, const
     return d;
 }
 
+PassMoments pass_moments(const std::vector<std::vector<Pixel>>& frames, int W, int H, bool gamma) {
+    if (W < 0 || H < 0) throw Error(RS_E_INVALID, "pass_moments: negative size");
+    const size_t npx = (size_t)W * (size_t)H;
+    std::vector<const float*> ptrs;
+    for (const std::vector<Pixel>& f : frames) {
+        if (f.size() != npx) throw Error(RS_E_INVALID, "pass_moments: frame size mismatch");
+        ptrs.push_back(reinterpret_cast<const float*>(f.data()));
+    }
+    if (ptrs.size() > 64) throw Error(RS_E_INVALID, "pass_moments: n_frames outside 1 .. 64");
+    PassMoments m{std::vector<Pixel>(npx, Pixel{0.f, 0.f, 0.f, 0.f}), std::vector<Pixel>(npx, Pixel{0.f, 0.f, 0.f, 0.f})};
+    check_rs(rs_pass_moments(ptrs.data(), (uint32_t)ptrs.size(), (uint32_t)W, (uint32_t)H, gamma ? 1 : 0,
+                             reinterpret_cast<float*>(m.mean.data()), reinterpret_cast<float*>(m.var.data())));
+    return m;
+}
+
+void denoise_var(std::vector<Pixel>& pixels, const std::vector<Pixel>& var, const std::vector<Pixel>* albedo,
+                 const std::vector<Pixel>* normal, int W, int H, const DenoiseVarSettings& settings, bool gamma,
+                 std::vector<Pixel>* out_var) {
+    if (W < 0 || H < 0) throw Error(RS_E_INVALID, "denoise: negative size");
+    const size_t npx = (size_t)W * (size_t)H;
+    if (pixels.size() != npx || var.size() != npx || (albedo && albedo->size() != npx) || (normal && normal->size() != npx))
+        throw Error(RS_E_INVALID, "denoise: frame size mismatch");
+    std::vector<Pixel> ov;
+    if (out_var) ov.assign(npx, Pixel{0.f, 0.f, 0.f, 0.f});
+    float* px = reinterpret_cast<float*>(pixels.data());
+    check_rs(rs_denoise_var(px, reinterpret_cast<const float*>(var.data()),
+                            albedo ? reinterpret_cast<const float*>(albedo->data()) : nullptr,
+                            normal ? reinterpret_cast<const float*>(normal->data()) : nullptr, (uint32_t)W, (uint32_t)H,
+                            settings.levels, settings.k_color, settings.sigma_normal, settings.sigma_depth, gamma ? 1 : 0,
+                            px, out_var ? reinterpret_cast<float*>(ov.data()) : nullptr));
+    if (out_var) *out_var = std::move(ov);
+}
+
+TakePhotoSettings::DenoisedPasses TakePhotoSettings::shot_denoised_passes(World& world, size_t passes,
+                                                                          const PixelController* pixel_map,
+                                                                          const DenoiseVarSettings& settings) {
+    if (passes < 2) throw Error(RS_E_INVALID, "shot_denoised_passes: fewer than 2 passes");
+    const uint32_t first = pass_;
+    std::vector<std::vector<Pixel>> frames;
+    try {
+        for (size_t k = 0; k < passes; ++k) {
+            pass_ = first + (uint32_t)k;
+            frames.push_back(shot_to_target(nullptr, world, nullptr, nullptr, pixel_map));
+        }
+    } catch (...) {
+        pass_ = first;
+        throw;
+    }
+    pass_ = first;
+    const rs_render_stats last_pass_stats = stats_;
+    const Features f = shot_features(world, pixel_map);
+    stats_ = last_pass_stats;
+    const int W = (int)camera_.desc().width, H = (int)camera_.desc().height;
+    PassMoments m = pass_moments(frames, W, H, gamma_);
+    DenoisedPasses d;
+    d.denoised = m.mean;
+    denoise_var(d.denoised, m.var, &f.albedo, &f.normal, W, H, settings, gamma_);
+    d.mean = std::move(m.mean);
+    d.var = std::move(m.var);
+    return d;
+}
+
 std::vector<Pixel> TakePhotoSettings::shot_to_target(const char*, World& world, PainterTarget* target,
                                                      PainterController*, const PixelController* pixel_map) {
     const rs_camera_desc& cam = camera_.desc();
