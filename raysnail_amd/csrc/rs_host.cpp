@@ -400,8 +400,11 @@ struct rs_scene {
         throw Error(RS_E_INVALID, "unknown object kind");
     }
 
-    // true when hit() over [tmin, e) is hit() over [tmin, inf) filtered by t1 < e: then the
-    // closest hit does not depend on the order objects are tested in (up to exact ties)
+    // true when hit() over [tmin, e) is hit() over [tmin, inf) filtered by t1 < e: then the hit flag and t1 of the
+    // closest hit do not depend on the order objects are tested in, nor does the record where one object alone
+    // has that t1. Objects hit at exactly the same t1 tie: the one the ray's walk tests first wins (a triangle
+    // tested later replaces it: Triangle::hit's range is closed at its end), and that order depends on the ray --
+    // as the reference's winner depends on its tree (tests/test_gpu_edge_rays.py)
     bool monotone(uint32_t h) const {
         const HObj& o = objs[h];
         if (o.kind == PK_SPHERE || o.kind == PK_RECT || o.kind == PK_TRIANGLE) return true;

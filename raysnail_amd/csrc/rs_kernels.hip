@@ -172,6 +172,13 @@ __device__ __forceinline__ bool slab64(const double lo[3], const double hi[3], c
 // rounding of o and of the precomputed products o'*inv (each <= |o| 2^-24); t at a plane is then one
 // FMA, t = lo*inv - (o+d)*inv. The remaining roundings (inv, fma) are relative and covered by a
 // 2^-18 slack on the interval. |inv| is clamped to 1e30 so no inf*0 / inf-inf appears.
+// An axis whose inv is infinite (a direction component that is +-0 or so small that 1 / d overflows) constrains
+// the exact test through the origin alone: (plane - o) * inf is +-inf, or a NaN that f64 min / max ignore when the
+// origin lies on the plane, so a box passes iff lo <= o <= hi. With the clamp the shift d stands in for that: the
+// far plane of a box the origin lies on gives t = d * 1e30, and d = 2^-100 (|o| = 0) made that 0.79, a range end
+// that culled every box farther than that along the ray. An axis whose inv overflows f32 gets an absolute 2^-20
+// in d instead, which puts that t beyond 9e23 whatever the origin (for a finite inv the wider box is merely
+// conservative).
 struct RayF {
     float inv[3], opi[3], omi[3];   // inv, (o+d)*inv, (o-d)*inv
 };
@@ -190,8 +197,9 @@ __device__ __forceinline__ RayF make_rayf(const V3& o, const V3& inv) {
 #pragma unroll
     for (int k = 0; k < 3; ++k) {
         const float of = (float)oo[k];
-        const float d = fabsf(of) * 0x1p-20f + 0x1p-100f;
-        const float iv = fminf(fmaxf((float)ii[k], -1e30f), 1e30f);
+        const float fi = (float)ii[k];
+        const float d = fabsf(of) * 0x1p-20f + (fabsf(fi) > 3e38f ? 0x1p-20f : 0x1p-100f);
+        const float iv = fminf(fmaxf(fi, -1e30f), 1e30f);
         r.inv[k] = iv;
         r.opi[k] = (of + d) * iv;
         r.omi[k] = (of - d) * iv;
@@ -2195,8 +2203,10 @@ __global__ __launch_bounds__(kBlock) void k_probe_hit(const DScene* __restrict__
     double* o = out + 13 * (size_t)i;
     for (int k = 0; k < 13; ++k) o[k] = 0.0;
     // range end handled by clamping best: world_hit starts from +inf, so emulate [tmin, tmax) by a
-    // post-check only when tmax is infinite (the render path always passes +inf)
-    if (world_hit<SM>(S, r, tmin, h, make_stk(S, stk_all)) && h.t1 < tmax) {
+    // post-check only when tmax is infinite (the render path always passes +inf). With tmax = +inf every hit
+    // stands, t1 = +inf included: Triangle::hit's range is closed at its end (triangle_mesh.rs), so a ray parallel
+    // to a triangle's plane can hit at infinity, and World::hit reports it.
+    if (world_hit<SM>(S, r, tmin, h, make_stk(S, stk_all)) && (h.t1 < tmax || tmax == RS_INF)) {
         o[0] = 1.0; o[1] = h.t1; o[2] = h.t2;
         o[3] = h.p.x; o[4] = h.p.y; o[5] = h.p.z; o[6] = h.n.x; o[7] = h.n.y; o[8] = h.n.z;
         if (S.uv) { o[9] = h.u; o[10] = h.v; }  // (u, v) exist only in scenes that read them
