@@ -559,6 +559,12 @@ void denoise_var(std::vector<Pixel>& pixels, const std::vector<Pixel>& var, cons
                  const std::vector<Pixel>* normal, int W, int H, const DenoiseVarSettings& settings = DenoiseVarSettings(),
                  bool gamma = true, std::vector<Pixel>* out_var = nullptr);
 
+// The adaptive pass loop's knobs (rs_render_adaptive, include/raysnail_adaptive.h); the defaults are the header's
+struct AdaptiveSettings {
+    uint32_t min_passes = RS_ADAPTIVE_MIN_PASSES, max_passes = RS_ADAPTIVE_MAX_PASSES, radius = RS_ADAPTIVE_RADIUS;
+    float tolerance = RS_ADAPTIVE_TOLERANCE, floor = RS_ADAPTIVE_FLOOR;
+};
+
 class TakePhotoSettings {  // src/camera.rs:103-154 + the GPU painter knobs (seed / pass / rows / mode)
 public:
     explicit TakePhotoSettings(const Camera& c) : camera_(c) {}
@@ -595,6 +601,14 @@ public:
     struct DenoisedPasses { std::vector<Pixel> denoised, mean, var; };
     DenoisedPasses shot_denoised_passes(World& world, size_t passes, const PixelController* pixel_map = nullptr,
                                         const DenoiseVarSettings& settings = DenoiseVarSettings());
+    // The adaptive pass loop from an empty image (rs_render_adaptive): passes pass_index, pass_index + 1, ... of
+    // `samples` each, every one rendered only where the running variance estimate (or min_passes) still asks for
+    // samples, pixel_map as the base mask. mean: the photo (gamma as set); var = [var_r, var_g, var_b, n] in linear
+    // radiance, n the passes the pixel got; passes: one report per rendered pass. last_stats() is the last pass's.
+    // Throws Error: RS_E_INVALID on a bad setting (before anything is rendered), RS_E_STATE on a host-only build.
+    struct Adaptive { std::vector<Pixel> mean, var; std::vector<rs_adaptive_pass> passes; };
+    Adaptive shot_adaptive(World& world, const AdaptiveSettings& settings = AdaptiveSettings(),
+                           const PixelController* pixel_map = nullptr);
     const rs_render_stats& last_stats() const { return stats_; }
 private:
     std::vector<uint8_t> mask_of(const PixelController* pixel_map) const;

@@ -564,4 +564,9 @@ int rs_probe_samples(rs_scene* s, const rs_camera_desc* cam, const rs_render_set
 #ifdef __cplusplus
 }
 #endif
+
+/* adaptive sampling (rs_moments_update_device, rs_moments_resolve_device, rs_adaptive_mask_device,
+ * rs_render_adaptive[_device]): additive extensions of ABI 6, declared in a header of their own */
+#include "raysnail_adaptive.h"
+
 #endif /* RAYSNAIL_HIP_H */

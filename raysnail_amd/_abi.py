@@ -61,6 +61,12 @@ RS_DENOISE_SIGMA_DEPTH = 0.1
 RS_DENOISE_VAR_LEVELS = 5
 RS_DENOISE_VAR_K_COLOR = 2.5
 RS_DENOISE_VAR_EPS = 1e-6
+# the adaptive pass loop's (include/raysnail_adaptive.h RS_ADAPTIVE_*)
+RS_ADAPTIVE_MIN_PASSES = 2
+RS_ADAPTIVE_MAX_PASSES = 32
+RS_ADAPTIVE_RADIUS = 1
+RS_ADAPTIVE_TOLERANCE = 0.1
+RS_ADAPTIVE_FLOOR = 0.03
 
 
 class rs_texture_desc(C.Structure):
@@ -113,6 +119,19 @@ class rs_scene_info(C.Structure):
                 ("tree_depth", C.c_int32), ("stack_need", C.c_int32), ("stack_lds", C.c_int32),
                 ("n_nodes", C.c_uint64), ("n_objects", C.c_uint64), ("n_world", C.c_uint64),
                 ("n_devices", C.c_int32), ("class_mask", C.c_uint32)]
+
+
+class rs_adaptive_stats(C.Structure):
+    _fields_ = [("active", C.c_uint64), ("hot", C.c_uint64), ("nonfinite", C.c_uint64), ("max_err2", C.c_float)]
+
+
+class rs_adaptive_settings(C.Structure):
+    _fields_ = [("min_passes", C.c_uint32), ("max_passes", C.c_uint32), ("radius", C.c_uint32),
+                ("tolerance", C.c_float), ("floor", C.c_float)]
+
+
+class rs_adaptive_pass(C.Structure):
+    _fields_ = [("active", C.c_uint64), ("hot", C.c_uint64), ("max_err2", C.c_float), ("stats", rs_render_stats)]
 
 
 KERNEL_NAMES = {0: None, 1: "k_path_mega", 2: "k_wf_extend", 3: "k_wfs_extend", 4: "k_features"}
@@ -205,6 +224,20 @@ def load() -> C.CDLL:
     lib.rs_denoise_var.argtypes = [VP, VP, VP, VP, C.c_uint32, C.c_uint32, C.c_uint32, C.c_float, C.c_float, C.c_float,
                                    C.c_int32, VP, VP]
     lib.rs_denoise_var.restype = C.c_int
+    lib.rs_moments_update_device.argtypes = [VP, VP, C.POINTER(VP), C.c_uint32, C.c_uint32, C.c_uint32, C.c_int32, VP]
+    lib.rs_moments_update_device.restype = C.c_int
+    lib.rs_moments_resolve_device.argtypes = [VP, VP, C.c_uint32, C.c_uint32, C.c_int32, VP, VP, VP]
+    lib.rs_moments_resolve_device.restype = C.c_int
+    lib.rs_adaptive_mask_device.argtypes = [VP, VP, VP, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_float,
+                                            C.c_float, C.c_uint32, VP, VP, C.POINTER(rs_adaptive_stats)]
+    lib.rs_adaptive_mask_device.restype = C.c_int
+    lib.rs_render_adaptive_device.argtypes = [VP, C.POINTER(rs_camera_desc), C.POINTER(rs_render_settings),
+                                              C.POINTER(rs_adaptive_settings), VP, VP, VP, VP, VP, VP,
+                                              C.POINTER(rs_adaptive_pass), U32P]
+    lib.rs_render_adaptive_device.restype = C.c_int
+    lib.rs_render_adaptive.argtypes = [VP, C.POINTER(rs_camera_desc), C.POINTER(rs_render_settings),
+                                       C.POINTER(rs_adaptive_settings), VP, VP, VP, C.POINTER(rs_adaptive_pass), U32P]
+    lib.rs_render_adaptive.restype = C.c_int
     lib.rs_probe_samples.argtypes = [VP, C.POINTER(rs_camera_desc), C.POINTER(rs_render_settings), C.c_uint32,
                                      C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p]
     lib.rs_probe_samples.restype = C.c_int
@@ -250,4 +283,10 @@ EXPORTED_SYMBOLS = [
     "rs_denoise_device", "rs_denoise",
     "rs_pass_moments_device", "rs_pass_moments", "rs_denoise_var_device", "rs_denoise_var",
     "rs_probe_world_hit", "rs_probe_samples",
+]
+
+# every symbol include/raysnail_adaptive.h declares (checked by tests/test_adaptive_abi.py)
+ADAPTIVE_SYMBOLS = [
+    "rs_moments_update_device", "rs_moments_resolve_device", "rs_adaptive_mask_device", "rs_render_adaptive_device",
+    "rs_render_adaptive",
 ]

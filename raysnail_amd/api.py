@@ -668,6 +668,39 @@ class DeviceScene:
                                                             stream_ptr or None, C.byref(out) if stats else None), "rs_")
         return out
 
+    def render_adaptive_device(self, cam: A.rs_camera_desc, st: A.rs_render_settings, settings: "AdaptiveSettings",
+                               d_acc_ptr: int, d_m2_ptr: int, d_work_frame_ptr: int, d_work_mask_ptr: int,
+                               d_base_mask_ptr: int = 0, stream_ptr: int = 0, reports: bool = True):
+        """rs_render_adaptive_device: the adaptive pass loop on the caller's device state (acc, m2: zero-filled for a
+        fresh image) and work buffers (a frame and a byte mask). Returns the list of rs_adaptive_pass reports, one per
+        rendered pass (reports=False: the number of passes; the renders then take no statistics)."""
+        a = settings.desc()
+        # (an invalid max_passes is the library's to refuse: no report array is sized by it)
+        passes = (A.rs_adaptive_pass * max(1, a.max_passes if a.max_passes <= 4096 else 1))() if reports else None
+        n = C.c_uint32()
+        _check(self.lib, self.lib.rs_render_adaptive_device(self.handle, C.byref(cam), C.byref(st), C.byref(a),
+                                                            d_base_mask_ptr or None, d_acc_ptr or None, d_m2_ptr or None,
+                                                            d_work_frame_ptr or None, d_work_mask_ptr or None,
+                                                            stream_ptr or None, passes, C.byref(n)), "rs_")
+        return [passes[k] for k in range(n.value)] if reports else n.value
+
+    def render_adaptive(self, cam: A.rs_camera_desc, st: A.rs_render_settings, settings: "AdaptiveSettings",
+                        base_mask: Optional[np.ndarray] = None):
+        """rs_render_adaptive: the loop from an empty state with host buffers. Returns (mean, var, reports): mean in
+        render's convention, var = [var_r, var_g, var_b, n] (n: the passes the pixel got), the per-pass reports."""
+        H, W = cam.height, cam.width
+        a = settings.desc()
+        mptr = None
+        if base_mask is not None:
+            base_mask = np.ascontiguousarray(base_mask, dtype=np.uint8).reshape(H * W)
+            mptr = base_mask.ctypes.data_as(C.c_void_p)
+        mean, var = np.zeros((H, W, 4), np.float32), np.zeros((H, W, 4), np.float32)
+        passes = (A.rs_adaptive_pass * max(1, a.max_passes if a.max_passes <= 4096 else 1))()
+        n = C.c_uint32()
+        _check(self.lib, self.lib.rs_render_adaptive(self.handle, C.byref(cam), C.byref(st), C.byref(a), mptr,
+                                                     mean.ctypes.data, var.ctypes.data, passes, C.byref(n)), "rs_")
+        return mean, var, [passes[k] for k in range(n.value)]
+
 
 # --------------------------------------------------------------------------- denoiser ----
 @dataclass
@@ -793,6 +826,56 @@ def denoise_var_device(d_beauty_ptr: int, d_var_ptr: int, d_albedo_ptr: int, d_n
                                           d_normal_ptr or None, width, height, st.levels, st.k_color, st.sigma_normal,
                                           st.sigma_depth, int(bool(gamma)), d_out_ptr or None, d_out_var_ptr or None,
                                           d_work_ptr or None, stream_ptr or None), "rs_")
+
+
+# ------------------------------------------------------------------- adaptive sampling ----
+@dataclass
+class AdaptiveSettings:
+    """The adaptive pass loop's knobs; the defaults are the header's RS_ADAPTIVE_* (include/raysnail_adaptive.h)."""
+    min_passes: int = A.RS_ADAPTIVE_MIN_PASSES
+    max_passes: int = A.RS_ADAPTIVE_MAX_PASSES
+    radius: int = A.RS_ADAPTIVE_RADIUS
+    tolerance: float = A.RS_ADAPTIVE_TOLERANCE
+    floor: float = A.RS_ADAPTIVE_FLOOR
+
+    def desc(self) -> A.rs_adaptive_settings:
+        for v in (self.min_passes, self.max_passes, self.radius):
+            if not 0 <= int(v) <= 0xFFFFFFFF:
+                raise RaysnailError(A.RS_E_INVALID, "adaptive: setting outside uint32")
+        return A.rs_adaptive_settings(int(self.min_passes), int(self.max_passes), int(self.radius),
+                                      float(self.tolerance), float(self.floor))
+
+
+def moments_update_device(d_acc_ptr: int, d_m2_ptr: int, d_frame_ptrs: Sequence[int], width: int, height: int,
+                          gamma: bool = True, stream_ptr: int = 0) -> None:
+    """rs_moments_update_device: Welford's update of the device state (acc = [mean rgb, n], m2 = [M2 rgb, 0]) with
+    1 .. 64 device frames, in order. One launch on the stream, no synchronisation, no allocation."""
+    lib = A.load()
+    n = len(d_frame_ptrs)
+    ptrs = (C.c_void_p * max(1, n))(*[C.c_void_p(p or None) for p in d_frame_ptrs])
+    _check(lib, lib.rs_moments_update_device(d_acc_ptr or None, d_m2_ptr or None, ptrs, n, width, height,
+                                             int(gamma), stream_ptr or None), "rs_")
+
+
+def moments_resolve_device(d_acc_ptr: int, d_m2_ptr: int, width: int, height: int, d_mean_ptr: int, d_var_ptr: int,
+                           gamma: bool = True, stream_ptr: int = 0) -> None:
+    """rs_moments_resolve_device: the state as pass_moments' (mean, var) frames; either output pointer may be 0."""
+    lib = A.load()
+    _check(lib, lib.rs_moments_resolve_device(d_acc_ptr or None, d_m2_ptr or None, width, height, int(gamma),
+                                              d_mean_ptr or None, d_var_ptr or None, stream_ptr or None), "rs_")
+
+
+def adaptive_mask_device(d_acc_ptr: int, d_m2_ptr: int, d_base_ptr: int, width: int, height: int, min_n: int, max_n: int,
+                         tolerance: float, floor: float, radius: int, d_mask_ptr: int, stream_ptr: int = 0,
+                         stats: bool = True):
+    """rs_adaptive_mask_device: the next pass's sample mask from the state. stats=True: synchronises the stream and
+    returns rs_adaptive_stats; stats=False: one launch, returns None."""
+    lib = A.load()
+    out = A.rs_adaptive_stats() if stats else None
+    _check(lib, lib.rs_adaptive_mask_device(d_acc_ptr or None, d_m2_ptr or None, d_base_ptr or None, width, height,
+                                            min_n, max_n, tolerance, floor, radius, d_mask_ptr or None,
+                                            stream_ptr or None, C.byref(out) if stats else None), "rs_")
+    return out
 
 
 # ----------------------------------------------------------------------------- camera ----
@@ -1000,6 +1083,24 @@ class TakePhotoSettings:
         self.last_stats = stats
         mean, var = pass_moments(frames, self._gamma)
         return denoise_var(mean, var, albedo, normal, settings, self._gamma), mean, var
+
+    def shot_adaptive(self, world: World, settings: Optional[AdaptiveSettings] = None,
+                      pixel_map: Optional[PixelController] = None):
+        """The adaptive pass loop from an empty image: passes pass_index, pass_index + 1, ... of `samples` each, every
+        one rendered only where the running variance estimate (or min_passes) still asks for samples; pixel_map is the
+        base mask. Returns (mean, var, passes, reports): mean the photo (gamma as set), var = [var_r, var_g, var_b, n]
+        in linear radiance, passes = var's alpha as an (H, W) int array, reports = one rs_adaptive_pass per rendered
+        pass. last_stats is the last pass's. No reference counterpart."""
+        cam = self.camera.desc
+        mask = None
+        if pixel_map is not None and type(pixel_map) is not PixelController:
+            mask = np.array([[1 if pixel_map.calculate_pixel(x, y) else 0 for x in range(cam.width)]
+                             for y in range(cam.height)], dtype=np.uint8)
+        mean, var, reports = world.device_scene().render_adaptive(cam, self.settings(), settings or AdaptiveSettings(),
+                                                                  mask)
+        if reports:
+            self.last_stats = reports[-1].stats
+        return mean, var, var[..., 3].astype(np.int32), reports
 
     def shot(self, path, world: World) -> np.ndarray:
         """src/camera.rs:290-295 (path is ignored upstream too)."""

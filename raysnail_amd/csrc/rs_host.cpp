@@ -3331,6 +3331,193 @@ int rs_denoise_var(const float* beauty, const float* var, const float* albedo, c
     });
 }
 
+// ---- adaptive sampling (rs_adaptive.hip) ----
+static void validate_frame_size(uint32_t width, uint32_t height, const char* what) {
+    const uint64_t n = (uint64_t)width * height;
+    if (n == 0) throw Error(RS_E_INVALID, std::string(what) + ": empty frame");
+    if (n > 0x7FFFFFFFull) throw Error(RS_E_INVALID, std::string(what) + ": frame too large");
+}
+
+static void validate_adaptive(uint32_t min_n, uint32_t max_n, float tolerance, float floor, uint32_t radius) {
+    if (min_n < 2) throw Error(RS_E_INVALID, "adaptive: min passes below 2");
+    if (max_n < min_n || max_n > 4096) throw Error(RS_E_INVALID, "adaptive: max passes below min passes or above 4096");
+    for (float v : {tolerance, floor})
+        if (!(v >= 1e-6f && v <= 1e4f)) throw Error(RS_E_INVALID, "adaptive: tolerance or floor not finite or outside [1e-6, 1e4]");
+    if (radius > 4) throw Error(RS_E_INVALID, "adaptive: radius above 4");
+}
+
+int rs_moments_update_device(float* d_acc, float* d_m2, const float* const* d_frames, uint32_t n_frames, uint32_t width,
+                             uint32_t height, int32_t gamma, void* stream) {
+    return run([&] {
+        if (n_frames < 1 || n_frames > 64) throw Error(RS_E_INVALID, "moments_update: n_frames outside 1 .. 64");
+        if (gamma != 0 && gamma != 1) throw Error(RS_E_INVALID, "moments_update: gamma is not 0 or 1");
+        validate_frame_size(width, height, "moments_update");
+        if (!d_acc || !d_m2 || !d_frames) throw Error(RS_E_INVALID, "moments_update: null argument");
+        for (uint32_t k = 0; k < n_frames; ++k)
+            if (!d_frames[k]) throw Error(RS_E_INVALID, "moments_update: null frame pointer");
+        HIP_OK(launch_moments_update(d_acc, d_m2, d_frames, n_frames, width * height, gamma, (hipStream_t)stream));
+    });
+}
+
+int rs_moments_resolve_device(const float* d_acc, const float* d_m2, uint32_t width, uint32_t height, int32_t gamma,
+                              float* d_mean, float* d_var, void* stream) {
+    return run([&] {
+        if (gamma != 0 && gamma != 1) throw Error(RS_E_INVALID, "moments_resolve: gamma is not 0 or 1");
+        validate_frame_size(width, height, "moments_resolve");
+        if (!d_acc || !d_m2) throw Error(RS_E_INVALID, "moments_resolve: null argument");
+        if (!d_mean && !d_var) throw Error(RS_E_INVALID, "moments_resolve: null argument (both outputs)");
+        HIP_OK(launch_moments_resolve(d_acc, d_m2, width * height, gamma, d_mean, d_var, (hipStream_t)stream));
+    });
+}
+
+// The mask launch with its statistics read back through `d_counters`: 16 bytes of device memory (one pixel of a frame)
+// that the stream may overwrite at this point. Synchronises the stream.
+static void adaptive_mask_stats(const float* d_acc, const float* d_m2, const uint8_t* d_base, uint32_t width, uint32_t height,
+                                uint32_t min_n, uint32_t max_n, float tol2, float floor, uint32_t radius, uint8_t* d_mask,
+                                unsigned int* d_counters, hipStream_t st, rs_adaptive_stats* stats, const RowSet& rows) {
+    HIP_OK(hipMemsetAsync(d_counters, 0, 4 * sizeof(unsigned int), st));
+    HIP_OK(launch_adaptive_mask(d_acc, d_m2, d_base, width, height, min_n, max_n, tol2, floor, radius, d_mask, d_counters, st,
+                                rows.begin, rows.end, rows.step));
+    unsigned int out[4] = {0, 0, 0, 0};
+    HIP_OK(hipMemcpyAsync(out, d_counters, sizeof(out), hipMemcpyDeviceToHost, st));
+    HIP_OK(hipMemsetAsync(d_counters, 0, 4 * sizeof(unsigned int), st));  // (left as an all-zero pixel: see the loop)
+    HIP_OK(hipStreamSynchronize(st));
+    stats->active = out[0];
+    stats->hot = out[1];
+    stats->nonfinite = out[2];
+    std::memcpy(&stats->max_err2, &out[3], 4);
+}
+
+int rs_adaptive_mask_device(const float* d_acc, const float* d_m2, const uint8_t* d_base, uint32_t width, uint32_t height,
+                            uint32_t min_n, uint32_t max_n, float tolerance, float floor, uint32_t radius, uint8_t* d_mask,
+                            void* stream, rs_adaptive_stats* stats) {
+    return run([&] {
+        validate_adaptive(min_n, max_n, tolerance, floor, radius);
+        validate_frame_size(width, height, "adaptive_mask");
+        if (!d_acc || !d_m2 || !d_mask) throw Error(RS_E_INVALID, "adaptive_mask: null argument");
+        const float tol2 = tolerance * tolerance;
+        const hipStream_t st = (hipStream_t)stream;
+        if (!stats) {
+            HIP_OK(launch_adaptive_mask(d_acc, d_m2, d_base, width, height, min_n, max_n, tol2, floor, radius, d_mask,
+                                        nullptr, st, 0, height, 1));
+            return;
+        }
+        unsigned int* d = nullptr;
+        HIP_OK(hipMalloc((void**)&d, 4 * sizeof(unsigned int)));
+        try {
+            RowSet all;
+            all.end = height;
+            adaptive_mask_stats(d_acc, d_m2, d_base, width, height, min_n, max_n, tol2, floor, radius, d_mask, d, st, stats, all);
+        } catch (...) {
+            (void)hipStreamSynchronize(st);
+            (void)hipFree(d);
+            throw;
+        }
+        (void)hipFree(d);
+    });
+}
+
+// rs_render_adaptive_device's loop: mask, stop or render, update. The mask's counters are the first 16 bytes of the
+// work frame (its first pixel: every frame has one), which holds nothing between a pass's update and the next pass's render.
+static void render_adaptive_device(rs_scene* s, const rs_camera_desc* cam, const rs_render_settings* st,
+                                   const rs_adaptive_settings* as, const uint8_t* d_base, float* d_acc, float* d_m2,
+                                   float* d_work_frame, uint8_t* d_work_mask, hipStream_t stream,
+                                   rs_adaptive_pass* passes_out, uint32_t* n_passes_out) {
+    if (!as) throw Error(RS_E_INVALID, "null argument");
+    validate_adaptive(as->min_passes, as->max_passes, as->tolerance, as->floor, as->radius);
+    validate_render(s, cam, st);
+    validate_frame_size(cam->width, cam->height, "render_adaptive");
+    if (st->gamma != 0 && st->gamma != 1) throw Error(RS_E_INVALID, "render_adaptive: gamma is not 0 or 1");
+    if (!d_acc || !d_m2 || !d_work_frame || !d_work_mask) throw Error(RS_E_INVALID, "render_adaptive: null argument");
+    if (n_passes_out) *n_passes_out = 0;
+    const float tol2 = as->tolerance * as->tolerance;
+    const int dev0 = s->reps[0]->device;
+    // The call's row lattice (st->row_begin / row_end / row_step) is part of the base mask: rs_render_device leaves
+    // rows off it untouched, so they are never hot, never sampled, and keep their state. The work frame starts all
+    // zero and the renders write lattice rows only: every other pixel of it stays [0,0,0,0] (alpha 0: no sample)
+    // through the updates -- the counters' pixel too, which is zeroed again after every read-back.
+    const RowSet rows = replica_rows(cam, st, 0, 1);
+    {
+        DeviceGuard g(dev0);
+        HIP_OK(hipMemsetAsync(d_work_frame, 0, (size_t)cam->width * cam->height * 4 * sizeof(float), stream));
+    }
+    for (uint32_t p = 0;; ++p) {
+        rs_adaptive_stats ms{};
+        {
+            DeviceGuard g(dev0);
+            adaptive_mask_stats(d_acc, d_m2, d_base, cam->width, cam->height, as->min_passes, as->max_passes, tol2, as->floor,
+                                as->radius, d_work_mask, reinterpret_cast<unsigned int*>(d_work_frame), stream, &ms, rows);
+        }
+        if (ms.active == 0 || p == as->max_passes) break;
+        rs_render_settings sp = *st;
+        sp.pass = st->pass + p;
+        rs_render_stats one{};
+        render_frame_device(s, cam, &sp, d_work_mask, d_work_frame, stream, passes_out ? &one : nullptr);
+        {
+            DeviceGuard g(dev0);
+            const float* frames[1] = {d_work_frame};
+            HIP_OK(launch_moments_update(d_acc, d_m2, frames, 1, cam->width * cam->height, st->gamma, stream));
+        }
+        if (passes_out) {
+            passes_out[p].active = ms.active;
+            passes_out[p].hot = ms.hot;
+            passes_out[p].max_err2 = ms.max_err2;
+            passes_out[p].stats = one;
+        }
+        if (n_passes_out) *n_passes_out = p + 1;
+    }
+}
+
+int rs_render_adaptive_device(rs_scene* s, const rs_camera_desc* cam, const rs_render_settings* st,
+                              const rs_adaptive_settings* as, const uint8_t* d_base_mask, float* d_acc, float* d_m2,
+                              float* d_work_frame, uint8_t* d_work_mask, void* stream, rs_adaptive_pass* passes_out,
+                              uint32_t* n_passes_out) {
+    return run([&] {
+        render_adaptive_device(S(s), cam, st, as, d_base_mask, d_acc, d_m2, d_work_frame, d_work_mask, (hipStream_t)stream,
+                               passes_out, n_passes_out);
+    });
+}
+
+int rs_render_adaptive(rs_scene* s, const rs_camera_desc* cam, const rs_render_settings* st, const rs_adaptive_settings* as,
+                       const uint8_t* base_mask, float* mean, float* var, rs_adaptive_pass* passes_out,
+                       uint32_t* n_passes_out) {
+    return run([&] {
+        S(s);
+        if (!as) throw Error(RS_E_INVALID, "null argument");
+        validate_adaptive(as->min_passes, as->max_passes, as->tolerance, as->floor, as->radius);
+        validate_render(s, cam, st);
+        validate_frame_size(cam->width, cam->height, "render_adaptive");
+        if (st->gamma != 0 && st->gamma != 1) throw Error(RS_E_INVALID, "render_adaptive: gamma is not 0 or 1");
+        if (!mean && !var) throw Error(RS_E_INVALID, "render_adaptive: null argument (both outputs)");
+        DeviceGuard g(s->reps[0]->device);
+        const size_t npx = (size_t)cam->width * cam->height, frame = npx * 4 * sizeof(float), fl = npx * 4;
+        // one allocation: acc, m2 (zeroed: the empty state), the work frame, one output frame, the two byte planes
+        float* d = nullptr;
+        HIP_OK(hipMalloc((void**)&d, 4 * frame + 2 * npx));
+        float *d_acc = d, *d_m2 = d + fl, *d_work = d + 2 * fl, *d_out = d + 3 * fl;
+        uint8_t* d_wmask = reinterpret_cast<uint8_t*>(d + 4 * fl);
+        uint8_t* d_base = base_mask ? d_wmask + npx : nullptr;
+        try {
+            HIP_OK(hipMemset(d, 0, 2 * frame));
+            if (base_mask) HIP_OK(hipMemcpy(d_base, base_mask, npx, hipMemcpyHostToDevice));
+            render_adaptive_device(s, cam, st, as, d_base, d_acc, d_m2, d_work, d_wmask, nullptr, passes_out, n_passes_out);
+            if (mean) {
+                HIP_OK(launch_moments_resolve(d_acc, d_m2, (uint32_t)npx, st->gamma, d_out, nullptr, nullptr));
+                HIP_OK(hipMemcpy(mean, d_out, frame, hipMemcpyDeviceToHost));
+            }
+            if (var) {
+                HIP_OK(launch_moments_resolve(d_acc, d_m2, (uint32_t)npx, st->gamma, nullptr, d_out, nullptr));
+                HIP_OK(hipMemcpy(var, d_out, frame, hipMemcpyDeviceToHost));
+            }
+        } catch (...) {
+            (void)hipDeviceSynchronize();
+            (void)hipFree(d);
+            throw;
+        }
+        (void)hipFree(d);
+    });
+}
+
 int rs_probe_world_hit(rs_scene* s, const double* rays, uint32_t n, double tmin, double tmax, double* out) {
     return run([&] {
         S(s);

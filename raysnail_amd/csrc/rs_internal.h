@@ -235,6 +235,19 @@ hipError_t launch_pass_moments(const float* const* frames, uint32_t n_frames, ui
 hipError_t launch_denoise_var(const float* beauty, const float* var, const float* albedo, const float* normal,
                               uint32_t width, uint32_t height, uint32_t levels, float k_color, float inv_n, float inv_d,
                               int gamma, float* out, float* out_var, float* work, hipStream_t st);
+// The adaptive pass loop's kernels (rs_adaptive.hip; contracts in raysnail_adaptive.h). launch_moments_update: one
+// k_moments_update launch, the frame pointers in the argument block as launch_pass_moments'. launch_moments_resolve:
+// mean / var, either may be null. launch_adaptive_mask: min_n, max_n <= 4096; tol2 = tolerance^2; counters: four zeroed
+// device words (active, hot, nonfinite, max_err2's bits: one pixel's 16 bytes) or null (no statistics); rows outside
+// [row_begin, row_end) or off the row_step lattice count as base == 0 (all rows: 0, height, 1).
+hipError_t launch_moments_update(float* acc, float* m2, const float* const* frames, uint32_t n_frames, uint32_t n_pix,
+                                 int gamma, hipStream_t st);
+hipError_t launch_moments_resolve(const float* acc, const float* m2, uint32_t n_pix, int gamma, float* mean, float* var,
+                                  hipStream_t st);
+hipError_t launch_adaptive_mask(const float* acc, const float* m2, const uint8_t* base, uint32_t width, uint32_t height,
+                                uint32_t min_n, uint32_t max_n, float tol2, float floor, uint32_t radius, uint8_t* mask,
+                                unsigned int* counters, hipStream_t st, uint32_t row_begin, uint32_t row_end,
+                                uint32_t row_step);
 // acc[c * n_pix + pixel] += sum over the batch's samples in sample order (deterministic; item-major
 // radiance rad[3 * item + c], items sample-plane by sample-plane); the last batch writes into_color of the sum into the frame instead (k_finalize's
 // arithmetic, one launch less) and zeroes zero[0, n_zero) (the frame's queue counters) for the next

@@ -480,6 +480,27 @@ TakePhotoSettings::DenoisedPasses TakePhotoSettings::shot_denoised_passes(World&
     return d;
 }
 
+TakePhotoSettings::Adaptive TakePhotoSettings::shot_adaptive(World& world, const AdaptiveSettings& adaptive,
+                                                             const PixelController* pixel_map) {
+    const rs_camera_desc& cam = camera_.desc();
+    const size_t npx = (size_t)cam.width * cam.height;
+    const std::vector<uint8_t> mask = mask_of(pixel_map);
+    const rs_render_settings st = settings();
+    rs_adaptive_settings as;
+    as.min_passes = adaptive.min_passes; as.max_passes = adaptive.max_passes; as.radius = adaptive.radius;
+    as.tolerance = adaptive.tolerance; as.floor = adaptive.floor;
+    Adaptive a{std::vector<Pixel>(npx, Pixel{0.f, 0.f, 0.f, 0.f}), std::vector<Pixel>(npx, Pixel{0.f, 0.f, 0.f, 0.f}), {}};
+    // (an invalid max_passes is the library's to refuse: no report array is sized by it)
+    a.passes.resize(adaptive.max_passes <= 4096 ? adaptive.max_passes : 0);
+    uint32_t n = 0;
+    check_rs(rs_render_adaptive(world.device_scene(), &cam, &st, &as, mask.empty() ? nullptr : mask.data(),
+                                reinterpret_cast<float*>(a.mean.data()), reinterpret_cast<float*>(a.var.data()),
+                                a.passes.empty() ? nullptr : a.passes.data(), &n));
+    a.passes.resize(n);
+    if (n) stats_ = a.passes[n - 1].stats;
+    return a;
+}
+
 std::vector<Pixel> TakePhotoSettings::shot_to_target(const char*, World& world, PainterTarget* target,
                                                      PainterController*, const PixelController* pixel_map) {
     const rs_camera_desc& cam = camera_.desc();
