@@ -561,6 +561,16 @@ int rs_probe_world_hit(rs_scene* s, const double* rays, uint32_t n, double tmin,
 int rs_probe_samples(rs_scene* s, const rs_camera_desc* cam, const rs_render_settings* st, uint32_t x, uint32_t y,
                      uint32_t s0, uint32_t n, double* out);
 
+/* One level of ray_color (camera.rs:156-255) after world.hit, on n synthetic hit records, through the scene
+ * mode's own shading code. rows: n*18 doubles = [ray o.xyz, d.xyz, time, hit p.xyz, n.xyz, t1, outside, u, v,
+ * material id as rs_probe_world_hit reports it (-1: the world's default material)]. Row i draws from the stream
+ * seed_from_u64(rs_stream_key(seed, 0, i, 0)) and starts from throughput T = (1, 1, 1), radiance L = 0.
+ * out: n*18 doubles = [continues, L.xyz (the level's emission), T.xyz (the level's factor; (1, 1, 1) when the
+ * path ends), the next ray's o.xyz, d.xyz, time (the row's own ray when the path ends), the four RNG state words
+ * after the level]. The scene needs a lights list (RS_E_NO_LIGHTS); an id outside the scene's materials is
+ * RS_E_INVALID. Diagnostic (shading parity against the oracle on exact inputs); additive extension of ABI 6. */
+int rs_probe_shade(rs_scene* s, const double* rows, uint32_t n, uint64_t seed, double* out);
+
 #ifdef __cplusplus
 }
 #endif

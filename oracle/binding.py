@@ -62,6 +62,8 @@ def load(path: str = LIB_PATH) -> C.CDLL:
     lib.orc_scatter.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_uint64,
                                 C.POINTER(C.c_double)]
     lib.orc_scatter.restype = C.c_int
+    lib.orc_shade_level.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint64, C.c_void_p]
+    lib.orc_shade_level.restype = C.c_int
     lib.orc_set_trace.argtypes = [C.c_int]
     lib.orc_set_variant.argtypes = [C.c_int]
     lib.orc_set_axis_bits.argtypes = [C.c_uint64]
@@ -151,6 +153,17 @@ class OracleScene:
         _check(self.lib, self.lib.orc_world_hit(self.h, (C.c_double * 3)(*o), (C.c_double * 3)(*d), time, tmin, tmax,
                                                 out), "orc_")
         return list(out)
+
+    def shade_level(self, rows: np.ndarray, seed: int) -> np.ndarray:
+        """One level of ray_color on synthetic hit records (orc_shade_level): rows (n, 18) doubles = ray o d time,
+        hit p n t1 outside u v material id (-1: the default material); returns (n, 18) = continues, emitted, factor,
+        next ray o d time, the four RNG words after the level. Row i draws from stream_key(seed, 0, i, 0)."""
+        rows = np.ascontiguousarray(rows, dtype=np.float64)
+        assert rows.ndim == 2 and rows.shape[1] == 18
+        out = np.full(rows.shape, -7.0)
+        _check(self.lib, self.lib.orc_shade_level(self.h, rows.ctypes.data, len(rows), seed, out.ctypes.data), "orc_")
+        return out
+
 
 
 def rtow_balls(seed: int = 7) -> np.ndarray:

@@ -1628,5 +1628,78 @@ int orc_scatter(orc_scene* s, int32_t mat, const double ray_in[7], const double 
     out[15] = sr.pdf.value(g);
     return RS_OK;
 }
+// One level of ray_color (camera.rs:156-255) after world.hit on n synthetic hit records: the same statements as
+// ray_color above, the recursive call replaced by (1, 1, 1) and the level's pieces returned. rows: n*18 doubles =
+// [ray o, d, time, hit p, n, t1, outside, u, v, material id (-1: the world's default material)]; row i draws from
+// seed_from_u64(stream_key(seed, 0, i, 0)). out: n*18 doubles = [continues, emitted, the factor the recursion's
+// result is multiplied by ((1, 1, 1) when there is no recursion), the next ray o, d, time (the row's own ray when
+// there is none), the RNG's four words after the level].
+int orc_shade_level(orc_scene* s, const double* rows, uint32_t n, uint64_t seed, double* out) {
+    if (!s->s.committed) return fail(RS_E_STATE, "scene not committed");
+    const Scene& sc = s->s;
+    for (uint32_t i = 0; i < n; ++i) {
+        const double* q = rows + 18 * (size_t)i;
+        double* o = out + 18 * (size_t)i;
+        const Ray ray(Vec3(q[0], q[1], q[2]), Vec3(q[3], q[4], q[5]), q[6]);
+        HitRecord hit;
+        hit.point = Vec3(q[7], q[8], q[9]);
+        hit.normal = Vec3(q[10], q[11], q[12]);
+        hit.t1 = q[13]; hit.t2 = q[13]; hit.outside = q[14] != 0.0;
+        hit.u = q[15]; hit.v = q[16];
+        if (q[17] != -1.0) {
+            if (!(q[17] >= 0.0 && q[17] < (double)sc.materials.size() && q[17] == std::floor(q[17])))
+                return fail(RS_E_INVALID, "bad material");
+            hit.material = sc.mat((int32_t)q[17]);
+        }
+        FastRng rng = FastRng::seed_from_u64(stream_key(seed, 0, i, 0));
+        const Material* material = hit.material ? hit.material : &sc.default_material;
+        Vec3 emitted;
+        material->emitted(hit.u, hit.v, hit.point, emitted);
+        bool cont = false;
+        Vec3 factor(1.0, 1.0, 1.0);
+        Ray next = ray;
+        const Vec3 deeper(1.0, 1.0, 1.0);  // stands for ray_color(.., depth - 1, ..)
+        ScatterRecord srec;
+        if (material->scatter(ray, hit, rng, srec)) {
+            if (srec.skip_pdf) {
+                if (!srec.has_ray) return fail(RS_E_UNSUPPORTED, "skip_pdf without a ray: no material does that");
+                factor = mul_color(deeper, srec.color);
+                next = srec.ray;
+            } else {
+                if (sc.lights.empty()) return fail(RS_E_NO_LIGHTS, "pdf material and an empty lights list");
+                double light_multi = 1.0;
+                double pdf_val;
+                Ray scattered;
+                if (rng.gen() < 0.5) {
+                    pdf_val = 0.3183098861837907;
+                    Vec3 dir_to_light = sc.lights_random(hit.point, rng).unit();
+                    Settings st = material->settings();
+                    if (st.phong_factor > 0.0)
+                        light_multi += phong_highlight(-dir_to_light, ray.direction, hit.normal, st.phong_exponent, st.phong_factor);
+                    Vec3 start = (g_variant & ORC_VAR_LIGHT_FROM_POINT) ? hit.point : ray.at(hit.t1 - 0.0002);
+                    scattered = Ray(start, dir_to_light, ray.time);
+                } else {
+                    Vec3 sd = srec.pdf.generate(rng);
+                    pdf_val = srec.pdf.value(sd);
+                    scattered = Ray(hit.point, sd, ray.time);
+                }
+                if (pdf_val <= 0.0 || pdf_val != pdf_val) pdf_val = 1e-5;
+                double spv = srec.pdf.value(scattered.direction);
+                double mult = spv / pdf_val;
+                Vec3 sample_color = light_multi * deeper;
+                factor = mul_color(sample_color, srec.color) * mult;
+                next = scattered;
+            }
+            cont = true;
+        }
+        o[0] = cont ? 1.0 : 0.0;
+        o[1] = emitted.x; o[2] = emitted.y; o[3] = emitted.z;
+        o[4] = factor.x; o[5] = factor.y; o[6] = factor.z;
+        o[7] = next.origin.x; o[8] = next.origin.y; o[9] = next.origin.z;
+        o[10] = next.direction.x; o[11] = next.direction.y; o[12] = next.direction.z; o[13] = next.time;
+        o[14] = (double)rng.x; o[15] = (double)rng.y; o[16] = (double)rng.z; o[17] = (double)rng.w;
+    }
+    return RS_OK;
+}
 
 }  // extern "C"

@@ -241,6 +241,8 @@ def load() -> C.CDLL:
     lib.rs_probe_samples.argtypes = [VP, C.POINTER(rs_camera_desc), C.POINTER(rs_render_settings), C.c_uint32,
                                      C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p]
     lib.rs_probe_samples.restype = C.c_int
+    lib.rs_probe_shade.argtypes = [VP, VP, C.c_uint32, C.c_uint64, VP]
+    lib.rs_probe_shade.restype = C.c_int
     lib.rs_render.argtypes = [VP, C.POINTER(rs_camera_desc), C.POINTER(rs_render_settings), VP, VP,
                               C.POINTER(rs_render_stats)]
     lib.rs_render_device.argtypes = [VP, C.POINTER(rs_camera_desc), C.POINTER(rs_render_settings), VP, VP, VP,
@@ -282,7 +284,7 @@ EXPORTED_SYMBOLS = [
     "rs_scene_set_frames_in_flight", "rs_scene_set_workspace", "rs_render", "rs_render_rows", "rs_render_device", "rs_render_device_passes", "rs_render_features", "rs_render_features_device", "rs_combine_pixels_device", "rs_noise_map_device", "rs_noise_map",
     "rs_denoise_device", "rs_denoise",
     "rs_pass_moments_device", "rs_pass_moments", "rs_denoise_var_device", "rs_denoise_var",
-    "rs_probe_world_hit", "rs_probe_samples",
+    "rs_probe_world_hit", "rs_probe_samples", "rs_probe_shade",
 ]
 
 # every symbol include/raysnail_adaptive.h declares (checked by tests/test_adaptive_abi.py)

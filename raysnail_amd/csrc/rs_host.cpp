@@ -3563,6 +3563,35 @@ int rs_probe_samples(rs_scene* s, const rs_camera_desc* cam, const rs_render_set
     });
 }
 
+int rs_probe_shade(rs_scene* s, const double* rows, uint32_t n, uint64_t seed, double* out) {
+    return run([&] {
+        S(s);
+        if (!s->committed) throw Error(RS_E_STATE, "scene not committed");
+        if (!rows || !out) throw Error(RS_E_INVALID, "null argument");
+        if (s->reps.empty()) throw Error(RS_E_STATE, "scene committed without devices (host-only build)");
+        // the light branch draws next_u32() % n_lights (list.rs:51 panics on an empty list)
+        if (s->lights.empty()) throw Error(RS_E_NO_LIGHTS, "the shading probe needs a lights list");
+        for (uint32_t i = 0; i < n; ++i) {  // the material id indexes the device's material table
+            const double m = rows[18 * (size_t)i + 17];
+            if (!(m >= -1.0 && m < (double)s->mdesc.size() && m == std::floor(m)))
+                throw Error(RS_E_INVALID, "unknown material id");
+        }
+        Replica& R = *s->reps[0];
+        DeviceGuard g(R.device);
+        const size_t bytes = (size_t)n * 18 * sizeof(double);
+        double *dr = nullptr, *dout = nullptr;
+        HIP_OK(hipMalloc((void**)&dr, bytes + 8));
+        HIP_OK(hipMalloc((void**)&dout, bytes + 8));
+        HIP_OK(hipMemcpy(dr, rows, bytes, hipMemcpyHostToDevice));
+        // rs_stream_key(seed, 0, row, 0) = splitmix64(splitmix64(key_base ^ row) ^ 0)
+        const uint64_t key_base = splitmix64_h(splitmix64_h(seed) ^ 0ull);
+        HIP_OK(launch_probe_shade(R.ref(), dr, n, key_base, dout, s->scene_mode, nullptr));
+        HIP_OK(hipMemcpy(out, dout, bytes, hipMemcpyDeviceToHost));
+        (void)hipFree(dr);
+        (void)hipFree(dout);
+    });
+}
+
 int rs_render_rows(rs_scene* s, const rs_camera_desc* cam, const rs_render_settings* st, const uint8_t* mask,
                    float* out_rgba, uint32_t bands, rs_row_callback cb, void* user, rs_render_stats* stats) {
     return run([&] {

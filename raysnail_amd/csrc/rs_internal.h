@@ -148,6 +148,9 @@ struct FinalParams {
 // radiance -> rad[3 * item + c] (item-major, rs_kernels.hip put_rad, like every path kernel).
 hipError_t launch_probe_sample(const SceneRef& s, const DCamera& c, const PathParams& p, int sm, uint32_t x, uint32_t y,
                                uint32_t s0, uint32_t n, double* out, hipStream_t st);
+// one shade_step per row on a synthetic hit record (k_probe_shade<sm>: the scene mode's own shading)
+hipError_t launch_probe_shade(const SceneRef& s, const double* rows, uint32_t n, uint64_t key_base, double* out, int sm,
+                              hipStream_t st);
 hipError_t launch_path_mega(const SceneRef& s, const DCamera& c, const PathParams& p, int sm, double* rad,
                             unsigned long long* seg_counters, uint32_t max_blocks, hipStream_t st);
 // bounce-synchronous unsorted wavefront (flat / rich scenes): camera rays of a chunk, then per bounce

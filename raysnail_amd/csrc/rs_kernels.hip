@@ -199,7 +199,10 @@ __device__ __forceinline__ RayF make_rayf(const V3& o, const V3& inv) {
         const float of = (float)oo[k];
         const float fi = (float)ii[k];
         const float d = fabsf(of) * 0x1p-20f + (fabsf(fi) > 3e38f ? 0x1p-20f : 0x1p-100f);
-        const float iv = fminf(fmaxf(fi, -1e30f), 1e30f);
+        // a NaN inv (a NaN direction component) stays NaN: the exact test's min / max ignore that axis (aabb.rs:20-38
+        // through f64::max / min), and so do slab32's and slab4's; clamped, it became -1e30 and culled every box whose
+        // slab on that axis does not hold the origin
+        const float iv = fi != fi ? fi : fminf(fmaxf(fi, -1e30f), 1e30f);
         r.inv[k] = iv;
         r.opi[k] = (of + d) * iv;
         r.omi[k] = (of - d) * iv;
@@ -2243,6 +2246,38 @@ __global__ __launch_bounds__(kBlock) void k_probe_sample(const DScene* __restric
     out[4 * (size_t)i + 3] = (double)segs;
 }
 
+// Diagnostic: one level of ray_color after world.hit -- shade_step on a synthetic hit record (tests/ shading
+// parity on exact inputs; the oracle's orc_shade_level). Row i: rows[18 i ..] = ray o(3) d(3) time, hit p(3) n(3)
+// t1 outside u v material id (-1: the world's default material); its stream is that of pixel i, sample 0 under
+// key_base (camera_sample_xy's). out[18 i ..] = continues, L(3), T(3) (from L = 0, T = 1), the ray after the level
+// o(3) d(3) time (the row's own ray when the path ends), the four RNG state words after the level.
+template <int SM>
+__global__ __launch_bounds__(kBlock) void k_probe_shade(const DScene* __restrict__ Sp, const double* __restrict__ rows, uint32_t n,
+                                                       uint64_t key_base, double* __restrict__ out) {
+    const DScene& S = *Sp;  // the scene lives in device memory: no by-value copy in scratch
+    const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
+    if (i >= n) return;
+    const double* q = rows + 18 * (size_t)i;
+    Ray r;
+    r.o = ld3(q); r.d = ld3(q + 3); r.time = q[6];
+    r.key = 0;
+    Hit h;
+    h.p = ld3(q + 7); h.n = ld3(q + 10); h.t1 = q[13]; h.t2 = q[13];
+    h.outside = q[14] != 0.0 ? 1 : 0;
+    h.u = q[15]; h.v = q[16];
+    h.mat = (int32_t)q[17];
+    Rng rng;
+    rng.seed_from_u64(splitmix64(splitmix64(key_base ^ (uint64_t)i) ^ 0ull));  // camera_sample_xy's key: pixel i, sample 0
+    V3 T = v3(1.0, 1.0, 1.0);
+    V3 L = v3(0.0, 0.0, 0.0);
+    const bool cont = shade_step<SM>(S, true, h, r, T, L, rng);
+    double* o = out + 18 * (size_t)i;
+    o[0] = cont ? 1.0 : 0.0;
+    o[1] = L.x; o[2] = L.y; o[3] = L.z; o[4] = T.x; o[5] = T.y; o[6] = T.z;
+    o[7] = r.o.x; o[8] = r.o.y; o[9] = r.o.z; o[10] = r.d.x; o[11] = r.d.y; o[12] = r.d.z; o[13] = r.time;
+    o[14] = (double)rng.x; o[15] = (double)rng.y; o[16] = (double)rng.z; o[17] = (double)rng.w;
+}
+
 #if !defined(RS_TU) || RS_TU == 5 || RS_TU == 6
 // First-hit feature buffers: per pixel the mean over its N samples of the camera ray's first hit --
 // albedo and coverage into one RGBA f32 frame, shading normal and depth into another. Sample s of pixel p is the
@@ -2406,7 +2441,9 @@ hipError_t launch_features(const SceneRef& s, const DCamera& c, const PathParams
       (s, w, bounce, blocks, st))                                                                              \
     X(hipError_t, wf_shade, (const SceneRef& s, const WfState& w, uint32_t bounce, uint32_t depth, uint64_t n_items,  \
                              double* rad, uint32_t blocks, hipStream_t st), (s, w, bounce, depth, n_items, rad, blocks, st)) \
-    X(hipError_t, wf_occupancy, (int* e, int* sh), (e, sh))
+    X(hipError_t, wf_occupancy, (int* e, int* sh), (e, sh))                                                    \
+    X(hipError_t, probe_shade, (const SceneRef& s, const double* rows, uint32_t n, uint64_t key_base, double* out,  \
+                                hipStream_t st), (s, rows, n, key_base, out, st))
 #define RS_SORTED_LAUNCHERS(X)                                                                                 \
     X(hipError_t, wfs_extend, (const SceneRef& s, const DCamera& c, const PathParams& p, const WfState& w,       \
                                QEnt* const* queues, uint32_t it, const InjParams& inj, double* rad, uint32_t blocks, \
@@ -2429,6 +2466,14 @@ hipError_t probe_sample_sm(const SceneRef& s, const DCamera& c, const PathParams
     const uint32_t blocks = (n + kBlock - 1) / kBlock;
     if (!blocks) return hipSuccess;
     hipLaunchKernelGGL(k_probe_sample<SMC>, dim3(blocks), dim3(kBlock), 0, st, s.dev, c, p, x, y, s0, n, out);
+    return hipGetLastError();
+}
+
+template <int SMC>
+hipError_t probe_shade_sm(const SceneRef& s, const double* rows, uint32_t n, uint64_t key_base, double* out, hipStream_t st) {
+    const uint32_t blocks = (n + kBlock - 1) / kBlock;
+    if (!blocks) return hipSuccess;
+    hipLaunchKernelGGL(k_probe_shade<SMC>, dim3(blocks), dim3(kBlock), 0, st, s.dev, rows, n, key_base, out);
     return hipGetLastError();
 }
 
@@ -2575,6 +2620,12 @@ RS_SORTED_LAUNCHERS(RS_INSTANTIATE_SM)
 hipError_t launch_probe_sample(const SceneRef& s, const DCamera& c, const PathParams& p, int sm, uint32_t x, uint32_t y,
                                uint32_t s0, uint32_t n, double* out, hipStream_t st) {
     RS_SM_DISPATCH(sm, return probe_sample_sm<SMC>(s, c, p, x, y, s0, n, out, st));
+    return hipErrorInvalidValue;
+}
+
+hipError_t launch_probe_shade(const SceneRef& s, const double* rows, uint32_t n, uint64_t key_base, double* out, int sm,
+                              hipStream_t st) {
+    RS_SM_DISPATCH(sm, return probe_shade_sm<SMC>(s, rows, n, key_base, out, st));
     return hipErrorInvalidValue;
 }
 

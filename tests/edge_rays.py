@@ -27,7 +27,7 @@ from raysnail_amd.scenes import C32
 
 INF = float("inf")
 TMINS = (0.0, 1e-4, 0.5)
-FAMILIES = ("axis", "scaled", "near")
+FAMILIES = ("axis", "scaled", "near")   # (the `nonfinite` family is a table of its own: nonfinite_rays())
 # what DeviceScene(world, devices=[]).info() must say: (scene_mode, tree_arity or None, ref_order)
 EXPECT_INFO = {"spheres": (1, 4, 0), "spheres_moving": (1, 4, 0), "flat": (2, None, 0), "nest0": (3, None, 1),
                "nest2": (4, None, 1), "rich": (0, None, 1)}
@@ -253,6 +253,61 @@ def rays(name: str):
     return r, np.array(fam), np.array(twins)
 
 
+# ------------------------------------------------------------------------------- non-finite rays ----
+NONFINITE_KINDS = ("nan_dir", "nan_origin", "inf_dir", "nan_component")
+
+
+@functools.lru_cache(maxsize=None)
+def nonfinite_rays(name: str):
+    """Rays the path feeds itself after a degenerate level (a NaN refraction, unit(0) of a light sample, the NaN
+    point of a hit at infinity), kept apart from rays(): (rays (n, 7), kind (n,) index into NONFINITE_KINDS).
+
+    nan_dir: every direction component NaN, the origin on the lattice. nan_origin: a NaN direction from an origin
+    with one or with all components NaN (or infinite, as ray_at(inf) leaves them). inf_dir: one to three
+    components +-inf, the others from D_axis. nan_component: one NaN component in a D_axis direction, the lattice
+    origin -- not something shading produces, but the case in which the boxes' tests and the objects' disagree most:
+    a box test ignores the NaN axis, a rect's bounds test lets the NaN coordinate pass."""
+    nan = float("nan")
+    org = _origins()[5::37]                                  # 60 lattice origins
+    dirs = d_axis()
+    times = MOVING_TIMES if name == "spheres_moving" else (0.0,)
+    rows, kind = [], []
+
+    def add(o, d, k):
+        rows.append(np.concatenate([o, d, [times[len(rows) % len(times)]]]))
+        kind.append(k)
+
+    for o in org:
+        add(o, (nan, nan, nan), 0)
+    for i, o in enumerate(org):
+        bad = np.array(o)
+        bad[i % 3] = (nan, INF, -INF)[(i // 3) % 3]
+        add(bad, (nan, nan, nan), 1)
+        add((nan, nan, nan), (nan, nan, nan), 1)
+        add(bad, dirs[i % len(dirs)], 1)
+    for i, o in enumerate(org):
+        for j in range(3):
+            d = np.array(dirs[(7 * i + j) % len(dirs)])
+            d[j] = INF if (i + j) % 2 else -INF
+            add(o, d, 2)
+        add(o, ((INF, -INF)[i % 2], INF, -INF), 2)
+    for i, o in enumerate(_origins()[3::11]):                # 200 lattice origins
+        d = np.array(dirs[(5 * i) % len(dirs)])
+        d[i % 3] = nan
+        add(o, d, 3)
+    r = np.ascontiguousarray(np.array(rows))
+    assert not np.isfinite(r).all(axis=1).any()
+    r.setflags(write=False)
+    return r, np.array(kind)
+
+
+@functools.lru_cache(maxsize=None)
+def nonfinite_reference(name: str, tmin: float) -> np.ndarray:
+    rec = oracle_records(oracle(name), nonfinite_rays(name)[0], tmin)
+    rec.setflags(write=False)
+    return rec
+
+
 # ------------------------------------------------------------------------------- oracle ----
 @functools.lru_cache(maxsize=None)
 def _fast_hit():
@@ -322,16 +377,16 @@ def leaf_objects(w: World):
     return out
 
 
-def ties(name: str, tmin: float):
+def ties(name: str, tmin: float, r=None, ref=None):
     """For a near-first scene: (tied (n_obj, n) bool, recs (n_obj, n, 13)); a fraction of a second and some tens
     of megabytes, so not kept between tests. Object k alone in an oracle world
     gives recs[k] (material id mapped to the full world's); tied[k, i] says its t1 on ray i equals the world
     record's t1 -- bitwise, but for t1 = 0, where +0 and -0 tie: no comparison a traversal makes tells them apart,
     and two spheres touching at the ray's origin (tmin = 0, a tangent ray) give one each. Only rays the world hits
-    are evaluated."""
+    are evaluated. r, ref: another ray table of the scene and its oracle records (default: rays(), reference())."""
     from oracle.binding import OracleScene
-    r = rays(name)[0]
-    ref = reference(name, tmin)
+    if r is None:
+        r, ref = rays(name)[0], reference(name, tmin)
     w = world(name)
     hit_rows = np.flatnonzero(ref[:, 0] == 1.0).tolist()
     objs = leaf_objects(w)

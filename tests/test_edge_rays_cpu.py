@@ -107,3 +107,29 @@ def test_ties(name):
     assert n_tie >= 300 and n_differ >= 100, (n_tie, n_differ)
     if name == "flat":  # the coplanar rects' overlap is among them
         assert n_rects >= 100, n_rects
+
+
+@pytest.mark.parametrize("name", sorted(E.SCENES))
+def test_nonfinite_family(name):
+    """The non-finite rays, apart from rays(): every ray has a NaN or an infinity, every kind is there, and the
+    oracle is defined on them -- a NaN or an infinite direction component alone never hits (every object's t is NaN,
+    or the root box's range is empty), while a NaN origin coordinate or a single NaN direction component does hit
+    rects, boxes and triangles' planes wherever the scene has them, with NaNs in the record."""
+    r, kind = E.nonfinite_rays(name)
+    assert not np.isfinite(r).all(axis=1).any() and np.isfinite(E.rays(name)[0]).all()
+    assert [int((kind == k).sum()) for k in range(len(E.NONFINITE_KINDS))] == [60, 180, 240, 200]
+    d = r[:, 3:6]
+    assert np.isnan(d[kind == 0]).all() and np.isfinite(r[kind == 0, :3]).all()
+    assert np.isinf(d[kind == 2]).any(axis=1).all() and not np.isnan(r[kind == 2]).any()
+    assert (np.isnan(d[kind == 3]).sum(axis=1) == 1).all()
+    for tmin in E.TMINS:
+        ref = E.nonfinite_reference(name, tmin)
+        assert set(np.unique(ref[:, 0])) <= {0.0, 1.0}
+        assert (ref[(kind == 0) | (kind == 2), 0] == 0.0).all()
+        hits = (ref[:, 0] == 1.0) & ((kind == 1) | (kind == 3))
+        if name in ("spheres", "spheres_moving"):
+            assert not hits.any()
+        else:
+            assert int(hits.sum()) >= 40 and np.isnan(ref[hits, 3:6]).any(axis=1).all()
+            if name != "rich":                                  # (a ConstantMedium's t1 can itself be NaN)
+                assert np.isfinite(ref[hits, 1]).all()

@@ -129,6 +129,36 @@ def test_triangle_hit_at_infinity(gpu):
     assert n >= 20, n
 
 
+def _differs_nan_aware(a: np.ndarray, b: np.ndarray) -> np.ndarray:
+    """Elementwise: NaN against NaN is equal (no portable bit pattern), everything else by its bits."""
+    nan = np.isnan(b)
+    return (np.isnan(a) != nan) | ((E.bits(a) != E.bits(b)) & ~nan)
+
+
+@pytest.mark.parametrize("tmin", E.TMINS)
+@pytest.mark.parametrize("name", sorted(E.SCENES))
+def test_nonfinite_rays(gpu, name, tmin):
+    """Rays with NaN or infinite components (E.nonfinite_rays: what a degenerate level of shading hands to
+    World::hit): the hit flag and every field are the oracle's, NaNs by position and the rest bit for bit. A box
+    test ignores a NaN axis (aabb.rs's f64::max / min), so the f32 culls must too (make_rayf). Near-first scenes:
+    where several objects tie on t1 the record is one tied object's, as in test_near_first_records."""
+    r, kind = E.nonfinite_rays(name)
+    ds = E.world(name).device_scene()
+    got = np.full((len(r), 13), -7.0)
+    assert ds.lib.rs_probe_world_hit(ds.handle, r.ctypes.data, len(r), tmin, E.INF, got.ctypes.data) == 0
+    ref = E.nonfinite_reference(name, tmin)
+    bad = _differs_nan_aware(got, ref)
+    rows = np.flatnonzero(bad[:, :2].any(axis=1))
+    assert len(rows) == 0, (name, tmin, rows[:5], r[rows[:5]], got[rows[:5]], ref[rows[:5]])
+    rows = np.flatnonzero(bad.any(axis=1))
+    if name in E.NEAR_FIRST and len(rows):
+        tied, recs = E.ties(name, tmin, r, ref)
+        same = ~_differs_nan_aware(recs[:, rows, 1:13], np.broadcast_to(got[rows, 1:13], recs[:, rows, 1:13].shape))
+        ok = np.any(np.all(same, axis=2) & tied[:, rows], axis=0) & (tied[:, rows].sum(axis=0) >= 2)
+        rows = rows[~ok]
+    assert len(rows) == 0, (name, tmin, rows[:5], r[rows[:5]], got[rows[:5]], ref[rows[:5]])
+
+
 @pytest.mark.parametrize("mode", [A.RS_MODE_MEGAKERNEL, A.RS_MODE_WAVEFRONT])
 @pytest.mark.parametrize("where", ["plane", "centre", "surface"])
 @pytest.mark.parametrize("name", E.FRAME_SCENES)
