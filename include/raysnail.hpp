@@ -587,20 +587,24 @@ public:
     std::vector<Pixel> shot(const char* path, World& world) { return shot_to_target(path, world, nullptr, nullptr, nullptr); }
     // The photo's first-hit feature frames (rs_render_features; no reference counterpart): albedo = [r, g, b,
     // coverage] and normal = [nx, ny, nz, depth], W * H pixels each, with the settings' samples, seed, pass and rows
-    // (depth, gamma and mode do not apply) and pixel_map as the mask.
+    // (depth, gamma and mode do not apply) and pixel_map as the mask. max_specular > 0 (at most 16, or Error
+    // RS_E_INVALID): rs_render_features_specular, the frames at the end of each sample's chain of at most that many
+    // mirror / glass bounces, tinted by the chain.
     struct Features { std::vector<Pixel> albedo, normal; };
-    Features shot_features(World& world, const PixelController* pixel_map = nullptr);
-    // The photo and its feature frames (the same seed, pass, rows and mask), then denoise() with the photo's gamma.
-    // last_stats() is the beauty frame's.
+    Features shot_features(World& world, const PixelController* pixel_map = nullptr, uint32_t max_specular = 0);
+    // The photo and its feature frames (the same seed, pass, rows and mask; shot_features' max_specular =
+    // guide_specular), then denoise() with the photo's gamma. last_stats() is the beauty frame's.
     struct Denoised { std::vector<Pixel> denoised, beauty; };
     Denoised shot_denoised(World& world, const PixelController* pixel_map = nullptr,
-                           const DenoiseSettings& settings = DenoiseSettings());
+                           const DenoiseSettings& settings = DenoiseSettings(), uint32_t guide_specular = 0);
     // `passes` (>= 2, or Error RS_E_INVALID) progressive passes of the photo -- pass indices pass_index ..
     // pass_index + passes - 1, `samples` each, every frame what shot gives for that pass -- and the first pass's
-    // feature frames; then pass_moments() and denoise_var() with the photo's gamma. last_stats() is the last pass's.
+    // feature frames (shot_features' max_specular = guide_specular); then pass_moments() and denoise_var() with the
+    // photo's gamma. last_stats() is the last pass's.
     struct DenoisedPasses { std::vector<Pixel> denoised, mean, var; };
     DenoisedPasses shot_denoised_passes(World& world, size_t passes, const PixelController* pixel_map = nullptr,
-                                        const DenoiseVarSettings& settings = DenoiseVarSettings());
+                                        const DenoiseVarSettings& settings = DenoiseVarSettings(),
+                                        uint32_t guide_specular = 0);
     // The adaptive pass loop from an empty image (rs_render_adaptive): passes pass_index, pass_index + 1, ... of
     // `samples` each, every one rendered only where the running variance estimate (or min_passes) still asks for
     // samples, pixel_map as the base mask. mean: the photo (gamma as set); var = [var_r, var_g, var_b, n] in linear

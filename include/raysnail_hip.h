@@ -384,6 +384,43 @@ int rs_render_features_device(rs_scene* s, const rs_camera_desc* cam, const rs_r
                               const uint8_t* d_mask, float* d_out_albedo, float* d_out_normal, void* stream,
                               rs_render_stats* stats);
 
+/* ---- feature buffers through mirrors and glass: the end of each sample's specular chain ----
+ * rs_render_features with one difference: what a sample contributes. Camera sample, ray, mask, row lattice, the f64
+ * sum in sample order from +0.0 divided by (double)N and cast to f32, zero masked pixels, unwritten rows off the
+ * lattice, the gathering of several devices, NULL outputs and validation are rs_render_features'. max_specular > 16 is
+ * RS_E_INVALID (checked with the other arguments, before anything touches the device). A sample's chain, with
+ * T = (1, 1, 1) in f64, depth unset, k = 0 and ray = the camera ray:
+ *   loop            h = World::hit(ray, 0.0001, +inf) with medium key 0
+ *   miss, k == 0    0 in all 8 channels (as rs_render_features)
+ *   miss, k > 0     the chain escapes: albedo = T, coverage = 1, normal = the previous hit's, depth = the sum so far
+ *   hit             depth = (k == 0) ? t1 : depth + t1 (directions are unit vectors: the path length). The hit's
+ *                   material is resolved as rs_render_features' albedo resolves it (the world's default material
+ *                   where the object has none; MixedMaterial -> material_1 up to 16 times, no RNG draw)
+ *   specular hit    the resolved kind is RS_MAT_METAL or RS_MAT_DIELECTRIC and k < max_specular:
+ *     Metal         c = the f32 texture.color(u, v, point); rf = d - n * (2.0 * dot(d, n)) (metal.rs:104-118). If
+ *                   !(dot(rf, n) > 0.0) the hit is terminal (below). Else T = T * (double)c per channel and
+ *                   ray = (p, rf, time)
+ *     Dielectric    dielectric.rs:55-79 with reflect_prob taken as 0 (no draw; `glass` is ignored):
+ *                   cos_theta = dot(-d, n); sin_theta = sqrt(1.0 - cos_theta * cos_theta); refr = outside ?
+ *                   enter_refractive : outer_refractive. If refr * sin_theta > 1.0: nd = d - n * (2.0 * dot(d, n))
+ *                   (total internal reflection). Else rp = (d + cos_theta * n) * refr; rq = (-sqrt(1.0 - dot(rp, rp)))
+ *                   * n; nd = rp + rq. No fused multiply-add in any of it (the beauty path's arithmetic and order).
+ *                   T = T * (double)texture.even per channel; ray = (p, nd, time). A NaN direction goes on into the
+ *                   next World::hit as it does in the beauty path
+ *                   then ++k and loop
+ *   terminal hit    any other hit, a specular kind at k == max_specular included: albedo = T * (double)(the f32 albedo
+ *                   rs_render_features gives this hit) per channel, coverage = 1, normal = this hit's, depth
+ * At most max_specular + 1 World::hit calls per sample; stats->segments counts them. max_specular == 0 gives
+ * rs_render_features' frames bit for bit (1.0 * x is exact) through the same kernel. kernel_id stays
+ * RS_KERNEL_FEATURES. No Fresnel split: a dielectric's guide is what is seen through it. Additive extension of ABI 6. */
+int rs_render_features_specular(rs_scene* s, const rs_camera_desc* cam, const rs_render_settings* st,
+                                const uint8_t* mask, uint32_t max_specular, float* out_albedo, float* out_normal,
+                                rs_render_stats* stats);
+/* the same into device frames; pointers, stream and stats semantics as rs_render_features_device */
+int rs_render_features_specular_device(rs_scene* s, const rs_camera_desc* cam, const rs_render_settings* st,
+                                       const uint8_t* d_mask, uint32_t max_specular, float* d_out_albedo,
+                                       float* d_out_normal, void* stream, rs_render_stats* stats);
+
 /* ---- progressive passes (the CLI's pass loop, src/bin/raysnail.rs:311-427) ----
  * Device-resident frames (RGBA f32, W*H*4), all work on the caller's stream (NULL = default). */
 typedef struct rs_noise_stats {

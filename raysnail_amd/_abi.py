@@ -256,6 +256,12 @@ def load() -> C.CDLL:
     lib.rs_render_features_device.argtypes = [VP, C.POINTER(rs_camera_desc), C.POINTER(rs_render_settings), VP, VP, VP,
                                               VP, C.POINTER(rs_render_stats)]
     lib.rs_render_features_device.restype = C.c_int
+    lib.rs_render_features_specular.argtypes = [VP, C.POINTER(rs_camera_desc), C.POINTER(rs_render_settings), VP,
+                                                C.c_uint32, VP, VP, C.POINTER(rs_render_stats)]
+    lib.rs_render_features_specular.restype = C.c_int
+    lib.rs_render_features_specular_device.argtypes = [VP, C.POINTER(rs_camera_desc), C.POINTER(rs_render_settings), VP,
+                                                       C.c_uint32, VP, VP, VP, C.POINTER(rs_render_stats)]
+    lib.rs_render_features_specular_device.restype = C.c_int
     lib.rs_probe_world_hit.argtypes = [VP, VP, C.c_uint32, C.c_double, C.c_double, VP]
     lib.rs_scene_get_info.argtypes = [VP, C.POINTER(rs_scene_info)]
     lib.rs_scene_commit_devices.argtypes = [VP, C.POINTER(C.c_int), C.c_int]
@@ -281,7 +287,7 @@ EXPORTED_SYMBOLS = [
     "rs_scene_destroy", "rs_perlin", "rs_image", "rs_material", "rs_sphere", "rs_aarect", "rs_box", "rs_quadric", "rs_raymarcher", "rs_triangles", "rs_intersection",
     "rs_difference", "rs_transformed", "rs_constant_medium", "rs_world_add", "rs_lights_add", "rs_set_background", "rs_set_time_range",
     "rs_scene_commit", "rs_scene_commit_devices", "rs_scene_get_info", "rs_scene_set_lanes",
-    "rs_scene_set_frames_in_flight", "rs_scene_set_workspace", "rs_render", "rs_render_rows", "rs_render_device", "rs_render_device_passes", "rs_render_features", "rs_render_features_device", "rs_combine_pixels_device", "rs_noise_map_device", "rs_noise_map",
+    "rs_scene_set_frames_in_flight", "rs_scene_set_workspace", "rs_render", "rs_render_rows", "rs_render_device", "rs_render_device_passes", "rs_render_features", "rs_render_features_device", "rs_render_features_specular", "rs_render_features_specular_device", "rs_combine_pixels_device", "rs_noise_map_device", "rs_noise_map",
     "rs_denoise_device", "rs_denoise",
     "rs_pass_moments_device", "rs_pass_moments", "rs_denoise_var_device", "rs_denoise_var",
     "rs_probe_world_hit", "rs_probe_samples", "rs_probe_shade",

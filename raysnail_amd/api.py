@@ -635,10 +635,12 @@ class DeviceScene:
 
     def render_features(self, cam: A.rs_camera_desc, st: A.rs_render_settings, mask: Optional[np.ndarray] = None,
                         albedo: Optional[np.ndarray] = None, normal: Optional[np.ndarray] = None,
-                        want: Tuple[bool, bool] = (True, True)):
+                        want: Tuple[bool, bool] = (True, True), max_specular: int = 0):
         """rs_render_features: the first-hit feature frames (albedo = [r, g, b, coverage], normal = [nx, ny, nz,
         depth]; (H, W, 4) float32 each) and the call's stats. want: which of the two to render (the other is
-        None); albedo / normal: frames to write into (rows off the lattice keep their values)."""
+        None); albedo / normal: frames to write into (rows off the lattice keep their values). max_specular > 0:
+        rs_render_features_specular, the frames at the end of each sample's chain of at most that many mirror /
+        glass bounces (at most 16)."""
         H, W = cam.height, cam.width
         outs = []
         for buf, on in ((albedo, want[0]), (normal, want[1])):
@@ -654,18 +656,27 @@ class DeviceScene:
             mptr = mask.ctypes.data_as(C.c_void_p)
         stats = A.rs_render_stats()
         ptrs = [None if b is None else b.ctypes.data_as(C.c_void_p) for b in outs]
-        _check(self.lib, self.lib.rs_render_features(self.handle, C.byref(cam), C.byref(st), mptr, ptrs[0], ptrs[1],
-                                                     C.byref(stats)), "rs_")
+        if max_specular == 0:
+            rc = self.lib.rs_render_features(self.handle, C.byref(cam), C.byref(st), mptr, ptrs[0], ptrs[1], C.byref(stats))
+        else:
+            rc = self.lib.rs_render_features_specular(self.handle, C.byref(cam), C.byref(st), mptr, max_specular, ptrs[0],
+                                                      ptrs[1], C.byref(stats))
+        _check(self.lib, rc, "rs_")
         return outs[0], outs[1], stats
 
     def render_features_device(self, cam: A.rs_camera_desc, st: A.rs_render_settings, d_albedo_ptr: int,
-                               d_normal_ptr: int, stream_ptr: int = 0, d_mask_ptr: int = 0, stats: bool = True):
+                               d_normal_ptr: int, stream_ptr: int = 0, d_mask_ptr: int = 0, stats: bool = True,
+                               max_specular: int = 0):
         """rs_render_features_device: the feature frames into device memory (either pointer may be 0). stats as
-        render_device."""
+        render_device. max_specular > 0: rs_render_features_specular_device."""
         out = A.rs_render_stats() if stats else None
-        _check(self.lib, self.lib.rs_render_features_device(self.handle, C.byref(cam), C.byref(st), d_mask_ptr or None,
-                                                            d_albedo_ptr or None, d_normal_ptr or None,
-                                                            stream_ptr or None, C.byref(out) if stats else None), "rs_")
+        tail = (d_albedo_ptr or None, d_normal_ptr or None, stream_ptr or None, C.byref(out) if stats else None)
+        if max_specular == 0:
+            rc = self.lib.rs_render_features_device(self.handle, C.byref(cam), C.byref(st), d_mask_ptr or None, *tail)
+        else:
+            rc = self.lib.rs_render_features_specular_device(self.handle, C.byref(cam), C.byref(st), d_mask_ptr or None,
+                                                             max_specular, *tail)
+        _check(self.lib, rc, "rs_")
         return out
 
     def render_adaptive_device(self, cam: A.rs_camera_desc, st: A.rs_render_settings, settings: "AdaptiveSettings",
@@ -1039,35 +1050,40 @@ class TakePhotoSettings:
         out, self.last_stats = world.device_scene().render_rows(cam, st, on_row, mask)
         return out
 
-    def shot_features(self, world: World, pixel_map: Optional[PixelController] = None) -> Tuple[np.ndarray, np.ndarray]:
+    def shot_features(self, world: World, pixel_map: Optional[PixelController] = None,
+                      max_specular: int = 0) -> Tuple[np.ndarray, np.ndarray]:
         """The first-hit feature frames of the photo (no reference counterpart): albedo = [r, g, b, coverage] and
         normal = [nx, ny, nz, depth], (H, W, 4) float32 each, with the settings' samples, seed, pass and rows
-        (depth, gamma and mode do not apply) and pixel_map as the mask."""
+        (depth, gamma and mode do not apply) and pixel_map as the mask. max_specular > 0: the frames at the end of
+        each sample's specular chain (DeviceScene.render_features)."""
         cam = self.camera.desc
         mask = None
         if pixel_map is not None and type(pixel_map) is not PixelController:
             mask = np.array([[1 if pixel_map.calculate_pixel(x, y) else 0 for x in range(cam.width)]
                              for y in range(cam.height)], dtype=np.uint8)
-        albedo, normal, self.last_stats = world.device_scene().render_features(cam, self.settings(), mask)
+        albedo, normal, self.last_stats = world.device_scene().render_features(cam, self.settings(), mask,
+                                                                               max_specular=max_specular)
         return albedo, normal
 
     def shot_denoised(self, world: World, pixel_map: Optional[PixelController] = None,
-                      settings: Optional[DenoiseSettings] = None) -> Tuple[np.ndarray, np.ndarray]:
-        """The photo and its feature frames (the same seed, pass, rows and mask), then rs_denoise with the photo's
-        gamma: returns (denoised, beauty), (H, W, 4) float32 each. No reference counterpart."""
+                      settings: Optional[DenoiseSettings] = None,
+                      guide_specular: int = 0) -> Tuple[np.ndarray, np.ndarray]:
+        """The photo and its feature frames (the same seed, pass, rows and mask; shot_features' max_specular =
+        guide_specular), then rs_denoise with the photo's gamma: returns (denoised, beauty), (H, W, 4) float32 each.
+        No reference counterpart."""
         beauty = self.shot_to_target(None, world, None, None, pixel_map)
         stats = self.last_stats
-        albedo, normal = self.shot_features(world, pixel_map)
+        albedo, normal = self.shot_features(world, pixel_map, guide_specular)
         self.last_stats = stats  # the beauty frame's
         return denoise(beauty, albedo, normal, settings, self._gamma), beauty
 
     def shot_denoised_passes(self, world: World, passes: int, pixel_map: Optional[PixelController] = None,
-                             settings: Optional[DenoiseVarSettings] = None
+                             settings: Optional[DenoiseVarSettings] = None, guide_specular: int = 0
                              ) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
         """`passes` (>= 2) progressive passes of the photo -- pass indices pass_index .. pass_index + passes - 1,
         `samples` each, every frame what shot gives for that pass -- and the first pass's feature frames (the same
-        seed, rows and mask); then pass_moments and denoise_var with the photo's gamma: returns (denoised, mean, var),
-        (H, W, 4) float32 each. last_stats is the last pass's. No reference counterpart."""
+        seed, rows and mask; shot_features' max_specular = guide_specular); then pass_moments and denoise_var with the
+        photo's gamma: returns (denoised, mean, var), (H, W, 4) float32 each. last_stats is the last pass's. No reference counterpart."""
         if passes < 2:
             raise RaysnailError(A.RS_E_INVALID, "shot_denoised_passes: fewer than 2 passes")
         first = self._pass
@@ -1079,7 +1095,7 @@ class TakePhotoSettings:
         finally:
             self._pass = first
         stats = self.last_stats
-        albedo, normal = self.shot_features(world, pixel_map)
+        albedo, normal = self.shot_features(world, pixel_map, guide_specular)
         self.last_stats = stats
         mean, var = pass_moments(frames, self._gamma)
         return denoise_var(mean, var, albedo, normal, settings, self._gamma), mean, var

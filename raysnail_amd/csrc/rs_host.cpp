@@ -2561,9 +2561,14 @@ void render_frame_host(rs_scene* s, const rs_camera_desc* cam, const rs_render_s
 // not write in place takes its next frame slot's buffers (Slot::d_feat, d_mask) and waits for that slot's previous
 // frame; so does every replica whose tree spills the kernel's LDS stack to the replica's shared overflow array
 // (frame_slots is 1 there: such frames run one after the other).
+// max_specular: 0 for the first-hit entry points (k_features); rs_render_features_specular's otherwise (k_features_spec
+// on the same grid: a chain's walks follow one another on the lane's stack, each as deep as the first-hit walk, so the
+// overflow array sized for `grid` blocks below holds for it too).
 void render_features(rs_scene* s, const rs_camera_desc* cam, const rs_render_settings* st, const uint8_t* mask,
-                     float* out_albedo, float* out_normal, hipStream_t stream, bool host, rs_render_stats* stats) {
+                     uint32_t max_specular, float* out_albedo, float* out_normal, hipStream_t stream, bool host,
+                     rs_render_stats* stats) {
     if (!out_albedo && !out_normal) throw Error(RS_E_INVALID, "null argument: both feature frames");
+    if (max_specular > 16) throw Error(RS_E_INVALID, "max_specular must be at most 16");
     validate_render(s, cam, st);
     rs_render_stats acc{};
     const auto t0 = std::chrono::steady_clock::now();
@@ -2639,8 +2644,8 @@ void render_features(rs_scene* s, const rs_camera_desc* cam, const rs_render_set
                 HIP_OK(hipMemsetAsync(c, 0, sizeof(unsigned long long), p.S));
                 timed_event(p.e0, p.S);
             }
-            HIP_OK(launch_features(ds, make_camera(*cam), pp, d_a, d_n, (unsigned long long*)p.cnt.get(), s->scene_mode, wide,
-                                   p.S));
+            HIP_OK(launch_features(ds, make_camera(*cam), pp, max_specular, d_a, d_n, (unsigned long long*)p.cnt.get(),
+                                   s->scene_mode, wide, p.S));
             if (stats) timed_event(p.e1, p.S);
             if (!direct) {
                 const hipMemcpyKind kind = host ? hipMemcpyDeviceToHost : hipMemcpyDefault;
@@ -3111,14 +3116,29 @@ int rs_render_device_passes(rs_scene* s, const rs_camera_desc* cam, const rs_ren
 int rs_render_features(rs_scene* s, const rs_camera_desc* cam, const rs_render_settings* st, const uint8_t* mask,
                        float* out_albedo, float* out_normal, rs_render_stats* stats) {
     return run([&] {
-        render_features(S(s), cam, st, mask, out_albedo, out_normal, nullptr, true, stats);
+        render_features(S(s), cam, st, mask, 0, out_albedo, out_normal, nullptr, true, stats);
     });
 }
 
 int rs_render_features_device(rs_scene* s, const rs_camera_desc* cam, const rs_render_settings* st, const uint8_t* d_mask,
                               float* d_out_albedo, float* d_out_normal, void* stream, rs_render_stats* stats) {
     return run([&] {
-        render_features(S(s), cam, st, d_mask, d_out_albedo, d_out_normal, (hipStream_t)stream, false, stats);
+        render_features(S(s), cam, st, d_mask, 0, d_out_albedo, d_out_normal, (hipStream_t)stream, false, stats);
+    });
+}
+
+int rs_render_features_specular(rs_scene* s, const rs_camera_desc* cam, const rs_render_settings* st, const uint8_t* mask,
+                                uint32_t max_specular, float* out_albedo, float* out_normal, rs_render_stats* stats) {
+    return run([&] {
+        render_features(S(s), cam, st, mask, max_specular, out_albedo, out_normal, nullptr, true, stats);
+    });
+}
+
+int rs_render_features_specular_device(rs_scene* s, const rs_camera_desc* cam, const rs_render_settings* st,
+                                       const uint8_t* d_mask, uint32_t max_specular, float* d_out_albedo,
+                                       float* d_out_normal, void* stream, rs_render_stats* stats) {
+    return run([&] {
+        render_features(S(s), cam, st, d_mask, max_specular, d_out_albedo, d_out_normal, (hipStream_t)stream, false, stats);
     });
 }
 

@@ -219,8 +219,10 @@ hipError_t launch_probe_hit(const SceneRef& s, const double* rays, uint32_t n, d
 // First-hit feature buffers (k_features): the lattice pixels of p (n_pix_local, width, height, row_begin, row_step,
 // sqrt_spp, key_base, mask) into the full frames out_albedo = [r, g, b, coverage] and out_normal = [nx, ny, nz, depth]
 // (RGBA f32; either may be null). seg_counter (may be null): += the world.hit calls. At most max_blocks blocks.
-hipError_t launch_features(const SceneRef& s, const DCamera& c, const PathParams& p, float* out_albedo, float* out_normal,
-                           unsigned long long* seg_counter, int sm, uint32_t max_blocks, hipStream_t st);
+// max_specular (0 .. 16): 0 = the first hit (k_features); otherwise the end of each sample's specular chain of at most
+// that many bounces (k_features_spec).
+hipError_t launch_features(const SceneRef& s, const DCamera& c, const PathParams& p, uint32_t max_specular, float* out_albedo,
+                           float* out_normal, unsigned long long* seg_counter, int sm, uint32_t max_blocks, hipStream_t st);
 // The a-trous denoiser (rs_denoise.hip; contract in raysnail_hip.h): k_dn_prepare, then `levels` k_dn_atrous launches
 // ping-ponging between the two W H float4 halves of `work`, the last one finishing into `out` (which may be `beauty`).
 // albedo / normal may be null; ic[i] is level i's colour constant; width height <= 2^31 - 1 is the caller's check.

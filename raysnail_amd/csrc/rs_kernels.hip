@@ -23,8 +23,8 @@
 // mode, in parallel. RS_TU undefined: everything in one unit (tools/regs.sh, build_variant.sh);
 // RS_TU = -1: the common unit (mode-independent kernels, the launchers that dispatch on the scene
 // mode); RS_TU = k >= 0: scene mode k's launch_*_sm<k> instantiations only; RS_TU = 6: the feature
-// unit (k_features with the generic World::hit; no scene mode's launchers). RS_TU_SUFFIX names the
-// unit in its exported debug symbol (nothing, _c, _<k>).
+// unit (k_features and k_features_spec with the generic World::hit; no scene mode's launchers).
+// RS_TU_SUFFIX names the unit in its exported debug symbol (nothing, _c, _<k>).
 #define RS_PASTE_(a, b) a##b
 #define RS_PASTE(a, b) RS_PASTE_(a, b)
 #if !defined(RS_TU)
@@ -2298,6 +2298,73 @@ __device__ __forceinline__ void first_hit_albedo(const DScene& S, const Hit& h, 
     }
 }
 
+// One sample of the specular-chain guides (raysnail_hip.h, rs_render_features_specular): follow up to max_specular
+// deterministic bounces -- Metal's reflection (metal.rs:104-118), Dielectric's refraction or total internal
+// reflection with reflect_prob taken as 0 (dielectric.rs:55-79; shade_surface's arithmetic, no draw) -- from the
+// camera ray to the first other hit, and contribute that hit under the chain's tint T: f = [T albedo, 1, normal,
+// path length]. A chain that leaves the scene after a bounce contributes [T, 1, the last normal, the length so far];
+// a camera ray that misses leaves f at 0. segs: += the World::hit calls (at most max_specular + 1). One walk at a
+// time on the same stack, so a walk's depth is k_features'. No barrier and no return from inside the loop: the
+// caller's lanes meet again at its block barriers.
+template <int SM>
+__device__ __forceinline__ void features_chain(const DScene& S, Ray r, uint32_t max_specular, const Stk& stk, double f[8],
+                                               uint32_t& segs) {
+    V3 T = v3(1.0, 1.0, 1.0);
+    V3 n_prev = v3(0.0, 0.0, 0.0);
+    double depth = 0.0;
+    for (uint32_t k = 0;; ++k) {
+        Hit h;
+        ++segs;
+        if (!world_hit<SM>(S, r, 0.0001, h, stk)) {
+            if (k > 0) {  // the chain escapes: an opaque surface whose colour is the tint
+                f[0] = T.x; f[1] = T.y; f[2] = T.z; f[3] = 1.0;
+                f[4] = n_prev.x; f[5] = n_prev.y; f[6] = n_prev.z; f[7] = depth;
+            }
+            break;
+        }
+        depth = k == 0 ? h.t1 : depth + h.t1;
+        bool bounced = false;
+        if (k < max_specular) {
+            int mi = h.mat >= 0 ? h.mat : S.default_mat;
+            for (int j = 0; j < 16 && S.mats[mi].kind == RS_MAT_MIXED; ++j) mi = S.mats[mi].mix_a;  // first_hit_albedo's
+            const DMaterial& M = S.mats[mi];
+            if (M.kind == RS_MAT_METAL) {
+                const V3 rf = reflect_v(r.d, h.n);
+                if (dot(rf, h.n) > 0.0) {
+                    float c[3];
+                    tex_color<1>(S, M, h, c);
+                    T = v3(T.x * (double)c[0], T.y * (double)c[1], T.z * (double)c[2]);
+                    r.o = h.p; r.d = rf;
+                    bounced = true;
+                }
+            } else if (M.kind == RS_MAT_DIELECTRIC) {
+                V3 nd;
+                const double cos_theta = dot(-r.d, h.n);
+                const double sin_theta = sqrt(1.0 - cos_theta * cos_theta);
+                const double refr = h.outside ? M.enter_refractive : M.outer_refractive;
+                if (!(refr * sin_theta > 1.0)) {
+                    const V3 rp = (r.d + cos_theta * h.n) * refr;
+                    const V3 rq = (-sqrt(1.0 - len2(rp))) * h.n;
+                    nd = rp + rq;
+                } else {
+                    nd = reflect_v(r.d, h.n);
+                }
+                T = v3(T.x * (double)M.even[0], T.y * (double)M.even[1], T.z * (double)M.even[2]);
+                r.o = h.p; r.d = nd;
+                bounced = true;
+            }
+        }
+        if (!bounced) {  // terminal: any other material, a specular one at the limit, Metal's below-surface rejection
+            float c[3];
+            first_hit_albedo(S, h, c);
+            f[0] = T.x * (double)c[0]; f[1] = T.y * (double)c[1]; f[2] = T.z * (double)c[2]; f[3] = 1.0;
+            f[4] = h.n.x; f[5] = h.n.y; f[6] = h.n.z; f[7] = depth;
+            break;
+        }
+        n_prev = h.n;
+    }
+}
+
 // A wave traces nc = min(N, 64) samples of each of 64 / nc consecutive lattice pixels per chunk (one pixel's camera
 // rays walk nearly the same nodes), N > 64 in chunks of 64 samples of one pixel. The lanes' 8 channels
 // go through LDS ([channel][lane]); lane (pixel, channel) adds its pixel's samples in sample order, starting from
@@ -2398,32 +2465,131 @@ __global__ __launch_bounds__(kBlock, SM == kSmMarch ? 1 : 2) void k_features(
     }
 }
 
-// blocks: at most the grid the caller sized the stack overflow for (grid-stride over the wave groups)
+
+// The specular-chain variant: k_features with features_chain in place of the one World::hit, as a
+// kernel of its own. The two are kept as two texts on purpose: routing k_features through a shared body changed its
+// machine code (not its registers), and the first-hit kernel is to stay the binary it was.
 template <int SM>
-static hipError_t features_launch(const SceneRef& s, const DCamera& c, const PathParams& p, float* out_albedo,
-                                  float* out_normal, unsigned long long* seg_counter, uint32_t max_blocks, hipStream_t st) {
+__global__ __launch_bounds__(kBlock, SM == kSmMarch ? 1 : 2) void k_features_spec(
+    const DScene* __restrict__ Sp, DCamera C, PathParams P, uint32_t max_specular, float4* __restrict__ out_albedo,
+    float4* __restrict__ out_normal, unsigned long long* __restrict__ seg_counter) {
+    const DScene& S = *Sp;  // the scene lives in device memory: no by-value copy in scratch
+    __shared__ int stk_all[kStackMax * kBlock];
+    __shared__ double red_all[kBlock / 64][8 * 64];
+    __shared__ float4 res_all[kBlock / 64][2 * 64];
+    const Stk stk = make_stk(S, stk_all);
+    const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    double* const red = red_all[wave];
+    float* const res = reinterpret_cast<float*>(res_all[wave]);
+    const uint32_t N = P.sqrt_spp * P.sqrt_spp;
+    const uint32_t nc = N < 64 ? (N ? N : 1u) : 64u;  // samples of a pixel per chunk
+    const uint32_t ppw = 64 / nc;                     // pixels per wave group
+    const uint32_t n_chunks = (N + 63) / 64;
+    const uint64_t n_groups = ((uint64_t)P.n_pix_local + ppw - 1) / ppw;
+    const uint64_t n_gblocks = (n_groups + kBlock / 64 - 1) / (kBlock / 64);
+    const uint32_t lp = lane / nc, ls = lane - lp * nc;  // this lane's pixel of the group and sample of the chunk
+    const double sq = (double)P.sqrt_spp, hh = (double)P.height;
+    uint32_t segs = 0;
+    for (uint64_t gb = blockIdx.x; gb < n_gblocks; gb += gridDim.x) {
+        const uint64_t pl0 = (gb * (kBlock / 64) + wave) * ppw;  // the group's first lattice pixel
+        const uint64_t pl = pl0 + lp;
+        bool live = lp < ppw && pl < P.n_pix_local;
+        uint32_t x = 0, y = 0;
+        uint64_t pix = 0;
+        if (live) {
+            x = (uint32_t)(pl % P.width);
+            y = P.row_begin + (uint32_t)(pl / P.width) * P.row_step;
+            pix = (uint64_t)y * P.width + x;
+            live = !P.mask || P.mask[pix];  // painter.rs:204-210: a masked pixel traces nothing
+        }
+        double carry = 0.0;  // N > 64 (one pixel per wave): lane c's running sum of channel c
+        for (uint32_t ch = 0; ch < n_chunks; ++ch) {
+            const uint32_t s = ch * 64 + ls;
+            double f[8] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};  // a miss adds 0.0 to every channel
+            if (live && s < N) {
+                Rng rng;
+                rng.seed_from_u64(splitmix64(splitmix64(P.key_base ^ pix) ^ (uint64_t)s));
+                const uint32_t si = s % P.sqrt_spp, sj = s / P.sqrt_spp;
+                const double xo = (double)x + ((double)si + 0.5) / sq;
+                const double yo = (double)y + ((double)sj + 0.5) / sq;
+                const Ray r = camera_ray(C, xo / (double)P.width, (hh - 1.0 - yo) / hh, rng);  // medium key 0
+                features_chain<SM>(S, r, max_specular, stk, f, segs);  // (no barrier inside: lanes idle to the longest chain)
+            }
+#pragma unroll
+            for (int c = 0; c < 8; ++c) red[c * 64 + lane] = f[c];
+            __syncthreads();
+            const uint32_t cnt = N - ch * 64 < nc ? N - ch * 64 : nc;  // samples in this chunk
+            for (uint32_t pc = lane; pc < ppw * 8; pc += 64) {         // (pixel of the group, channel)
+                const double* src = red + (pc & 7u) * 64 + (pc >> 3) * nc;
+                double a = ch ? carry : 0.0;
+                for (uint32_t k = 0; k < cnt; ++k) a += src[k];
+                carry = a;
+                if (ch + 1 == n_chunks) res[pc] = (float)(a / (double)N);
+            }
+            __syncthreads();
+        }
+        if (n_chunks == 0) {  // no samples: 0 / 0, as the beauty frame's into_color
+            for (uint32_t pc = lane; pc < ppw * 8; pc += 64) res[pc] = (float)(0.0 / (double)N);
+            __syncthreads();
+        }
+        // the group's pixels: lanes [0, ppw) the albedo frame's float4, [ppw, 2 ppw) the normal frame's
+        for (uint32_t q = lane; q < 2 * ppw; q += 64) {
+            const uint32_t which = q >= ppw ? 1u : 0u, p = q - which * ppw;
+            const uint64_t qpl = pl0 + p;
+            float4* const o = which ? out_normal : out_albedo;
+            if (qpl < P.n_pix_local && o) {
+                const uint32_t qx = (uint32_t)(qpl % P.width);
+                const uint32_t qy = P.row_begin + (uint32_t)(qpl / P.width) * P.row_step;
+                const uint64_t qpix = (uint64_t)qy * P.width + qx;
+                float4 v = res_all[wave][p * 2 + which];
+                if (P.mask && !P.mask[qpix]) v = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+                o[qpix] = v;
+            }
+        }
+        // (the next group's barriers separate these reads of res from its writes)
+    }
+    if (seg_counter) {  // statistics: world.hit calls, one atomic per wave
+        unsigned long long s64 = segs;
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) s64 += __shfl_xor(s64, off, 64);
+        if (lane == 0 && s64) atomicAdd(seg_counter, s64);
+    }
+}
+
+
+// blocks: at most the grid the caller sized the stack overflow for (grid-stride over the wave groups).
+// max_specular == 0 launches k_features; anything else k_features_spec (the same grid: a chain's walks follow
+// one another on the lane's stack)
+template <int SM>
+static hipError_t features_launch(const SceneRef& s, const DCamera& c, const PathParams& p, uint32_t max_specular,
+                                  float* out_albedo, float* out_normal, unsigned long long* seg_counter,
+                                  uint32_t max_blocks, hipStream_t st) {
     const uint32_t N = p.sqrt_spp * p.sqrt_spp;
     const uint32_t ppw = 64 / (N < 64 ? (N ? N : 1u) : 64u);
     const uint64_t groups = ((uint64_t)p.n_pix_local + ppw - 1) / ppw;
     const uint64_t blocks = std::min<uint64_t>((groups + kBlock / 64 - 1) / (kBlock / 64), max_blocks);
     if (!blocks) return hipSuccess;
-    hipLaunchKernelGGL(k_features<SM>, dim3((uint32_t)blocks), dim3(kBlock), 0, st, s.dev, c, p,
-                       reinterpret_cast<float4*>(out_albedo), reinterpret_cast<float4*>(out_normal), seg_counter);
+    if (max_specular == 0)
+        hipLaunchKernelGGL(k_features<SM>, dim3((uint32_t)blocks), dim3(kBlock), 0, st, s.dev, c, p,
+                           reinterpret_cast<float4*>(out_albedo), reinterpret_cast<float4*>(out_normal), seg_counter);
+    else
+        hipLaunchKernelGGL(k_features_spec<SM>, dim3((uint32_t)blocks), dim3(kBlock), 0, st, s.dev, c, p, max_specular,
+                           reinterpret_cast<float4*>(out_albedo), reinterpret_cast<float4*>(out_normal), seg_counter);
     return hipGetLastError();
 }
 #if !defined(RS_TU) || RS_TU == 5
-hipError_t features_march(const SceneRef& s, const DCamera& c, const PathParams& p, float* out_albedo, float* out_normal,
-                          unsigned long long* seg_counter, uint32_t max_blocks, hipStream_t st) {
-    return features_launch<kSmMarch>(s, c, p, out_albedo, out_normal, seg_counter, max_blocks, st);
+hipError_t features_march(const SceneRef& s, const DCamera& c, const PathParams& p, uint32_t max_specular, float* out_albedo,
+                          float* out_normal, unsigned long long* seg_counter, uint32_t max_blocks, hipStream_t st) {
+    return features_launch<kSmMarch>(s, c, p, max_specular, out_albedo, out_normal, seg_counter, max_blocks, st);
 }
 #endif
 #if !defined(RS_TU) || RS_TU == 6
-hipError_t features_march(const SceneRef& s, const DCamera& c, const PathParams& p, float* out_albedo, float* out_normal,
-                          unsigned long long* seg_counter, uint32_t max_blocks, hipStream_t st);
-hipError_t launch_features(const SceneRef& s, const DCamera& c, const PathParams& p, float* out_albedo, float* out_normal,
-                           unsigned long long* seg_counter, int sm, uint32_t max_blocks, hipStream_t st) {
-    if (sm == kSmMarch) return features_march(s, c, p, out_albedo, out_normal, seg_counter, max_blocks, st);
-    return features_launch<kSmGeneric>(s, c, p, out_albedo, out_normal, seg_counter, max_blocks, st);
+hipError_t features_march(const SceneRef& s, const DCamera& c, const PathParams& p, uint32_t max_specular, float* out_albedo,
+                          float* out_normal, unsigned long long* seg_counter, uint32_t max_blocks, hipStream_t st);
+hipError_t launch_features(const SceneRef& s, const DCamera& c, const PathParams& p, uint32_t max_specular, float* out_albedo,
+                           float* out_normal, unsigned long long* seg_counter, int sm, uint32_t max_blocks, hipStream_t st) {
+    if (sm == kSmMarch) return features_march(s, c, p, max_specular, out_albedo, out_normal, seg_counter, max_blocks, st);
+    return features_launch<kSmGeneric>(s, c, p, max_specular, out_albedo, out_normal, seg_counter, max_blocks, st);
 }
 #endif
 #endif  // the feature unit or the marcher unit

@@ -381,15 +381,17 @@ std::vector<uint8_t> TakePhotoSettings::mask_of(const PixelController* pixel_map
     return mask;
 }
 
-TakePhotoSettings::Features TakePhotoSettings::shot_features(World& world, const PixelController* pixel_map) {
+TakePhotoSettings::Features TakePhotoSettings::shot_features(World& world, const PixelController* pixel_map,
+                                                             uint32_t max_specular) {
     const rs_camera_desc& cam = camera_.desc();
     const size_t npx = (size_t)cam.width * cam.height;
     const std::vector<uint8_t> mask = mask_of(pixel_map);
     Features f{std::vector<Pixel>(npx, Pixel{0.f, 0.f, 0.f, 0.f}), std::vector<Pixel>(npx, Pixel{0.f, 0.f, 0.f, 0.f})};
     const rs_render_settings st = settings();
-    check_rs(rs_render_features(world.device_scene(), &cam, &st, mask.empty() ? nullptr : mask.data(),
-                                reinterpret_cast<float*>(f.albedo.data()), reinterpret_cast<float*>(f.normal.data()),
-                                &stats_));
+    const uint8_t* m = mask.empty() ? nullptr : mask.data();
+    float *a = reinterpret_cast<float*>(f.albedo.data()), *n = reinterpret_cast<float*>(f.normal.data());
+    check_rs(max_specular == 0 ? rs_render_features(world.device_scene(), &cam, &st, m, a, n, &stats_)
+                               : rs_render_features_specular(world.device_scene(), &cam, &st, m, max_specular, a, n, &stats_));
     return f;
 }
 
@@ -407,11 +409,11 @@ void denoise(std::vector<Pixel>& pixels, const std::vector<Pixel>* albedo, const
 }
 
 TakePhotoSettings::Denoised TakePhotoSettings::shot_denoised(World& world, const PixelController* pixel_map,
-                                                             const DenoiseSettings& settings) {
+                                                             const DenoiseSettings& settings, uint32_t guide_specular) {
     Denoised d;
     d.beauty = shot_to_target(nullptr, world, nullptr, nullptr, pixel_map);
     const rs_render_stats beauty_stats = stats_;
-    const Features f = shot_features(world, pixel_map);
+    const Features f = shot_features(world, pixel_map, guide_specular);
     stats_ = beauty_stats;
     d.denoised = d.beauty;
     denoise(d.denoised, &f.albedo, &f.normal, (int)camera_.desc().width, (int)camera_.desc().height, settings, gamma_);
@@ -453,7 +455,8 @@ void denoise_var(std::vector<Pixel>& pixels, const std::vector<Pixel>& var, cons
 
 TakePhotoSettings::DenoisedPasses TakePhotoSettings::shot_denoised_passes(World& world, size_t passes,
                                                                           const PixelController* pixel_map,
-                                                                          const DenoiseVarSettings& settings) {
+                                                                          const DenoiseVarSettings& settings,
+                                                                          uint32_t guide_specular) {
     if (passes < 2) throw Error(RS_E_INVALID, "shot_denoised_passes: fewer than 2 passes");
     const uint32_t first = pass_;
     std::vector<std::vector<Pixel>> frames;
@@ -468,7 +471,7 @@ TakePhotoSettings::DenoisedPasses TakePhotoSettings::shot_denoised_passes(World&
     }
     pass_ = first;
     const rs_render_stats last_pass_stats = stats_;
-    const Features f = shot_features(world, pixel_map);
+    const Features f = shot_features(world, pixel_map, guide_specular);
     stats_ = last_pass_stats;
     const int W = (int)camera_.desc().width, H = (int)camera_.desc().height;
     PassMoments m = pass_moments(frames, W, H, gamma_);
