@@ -14,6 +14,7 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <atomic>
 #include <chrono>
 #include <functional>
 #include <cmath>
@@ -159,6 +160,19 @@ struct HostScene {
     std::vector<Blob> blobs;
 };
 
+// What a slot's candidate records depend on: the camera, the frame's size and row lattice, and the scene (the
+// generation its commit took). valid = false: no records (never built, or the build could not be enqueued).
+struct CandKey {
+    DCamera dc{};
+    uint32_t width = 0, height = 0, row_begin = 0, row_step = 0, n_pix = 0;
+    uint64_t gen = 0;
+    bool valid = false;
+    bool same(const CandKey& o) const {
+        return valid && o.valid && std::memcmp(&dc, &o.dc, sizeof(DCamera)) == 0 && width == o.width && height == o.height &&
+               row_begin == o.row_begin && row_step == o.row_step && n_pix == o.n_pix && gen == o.gen;
+    }
+};
+
 // One frame in flight on a replica: its streams and the render workspace it owns (grown on demand).
 // Frames are dealt to a replica's slots round robin; a frame waits only for the previous frame of
 // ITS slot (free_ev, recorded after the last kernel that reads the slot's buffers), so the next
@@ -188,6 +202,10 @@ struct Slot {
     // the same shape (Replica::hist)
     uint32_t* h_hist = nullptr; size_t hist_cap = 0, hist_words = 0; uint64_t hist_sig = 0;
     hipEvent_t hist_ev = nullptr; bool hist_pending = false;
+    // the spheres mode's candidate records (rs_cam_cand.h), one per lattice pixel, and what they were built for: the
+    // frames of one camera on this slot build them once. Written and read on the slot's own streams only.
+    uint4* d_cand = nullptr; size_t cand_cap = 0;
+    CandKey cand_key{};
 
     // wait until nothing in flight uses this slot's buffers
     void quiesce() {
@@ -201,7 +219,8 @@ struct Slot {
             if (lane[l]) (void)hipStreamSynchronize(lane[l]);
         if (acc_stream) (void)hipStreamSynchronize(acc_stream);
         if (free_rec) (void)hipEventSynchronize(free_ev);
-        for (void* p : {(void*)d_rad, (void*)d_acc, (void*)d_cnt, (void*)d_mask, (void*)d_out, (void*)d_feat, d_wf, (void*)d_counts})
+        for (void* p : {(void*)d_rad, (void*)d_acc, (void*)d_cnt, (void*)d_mask, (void*)d_out, (void*)d_feat, d_wf, (void*)d_counts,
+                        (void*)d_cand})
             if (p) (void)hipFree(p);
         for (uint32_t l = 0; l < kMaxLanes; ++l) {
             if (lane[l]) (void)hipStreamDestroy(lane[l]);
@@ -301,6 +320,8 @@ struct rs_scene {
     int tree_depth = 0;                     // levels of the tree in use
     int tree_arity = 0;                     // 4: 4-wide tree, 2: binary tree, 0: empty world
     int stack_need = 0;                     // exact worst-case traversal stack depth of that tree
+    uint64_t commit_gen = 0;                // the commit's number among all scenes' (the slots' CandKey: records built for
+                                            // another commit are never read)
     size_t n_nodes = 0;
     size_t n_leaf_entries = 0;
     double time0 = 0.0, time1 = 0.0;        // World::new time_limit (world.rs:40-53)
@@ -1314,6 +1335,11 @@ void commit(rs_scene* s, const int* devices, int n) {
         throw;
     }
     if (n > 0) HIP_OK(hipSetDevice(prev));
+    // candidate records are built for one commit: a new generation, and no slot's key survives it
+    static std::atomic<uint64_t> commits{0};
+    s->commit_gen = ++commits;
+    for (auto& R : s->reps)
+        for (Slot& L : R->slots) L.cand_key.valid = false;
     s->committed = true;
 }
 
@@ -1892,9 +1918,41 @@ void hist_end(const GridHist& h, Slot& L, const FrameSched& f, hipStream_t S) {
     L.hist_words = h.hwords;
 }
 
+// The candidate records for this frame's camera launches (cam_cand, rs_internal.h), or null. A scene gets them in
+// the spheres mode, without a moving sphere, on the near-first 4-wide tree, with leaf entries that fit a uint16 next
+// to the two marks and a stack the build kernel's fits; a frame, when its camera is usable (cand_camera) and its
+// records' byte offsets fit 32 bits. The slot's buffer is allocated on first use; a device without room for it
+// renders without records. A frame whose key differs from the slot's enqueues the build on L0, which every lane of
+// the frame starts after (fork_lanes) and which starts after the slot's previous frame (free_ev): no other stream
+// touches the buffer.
+bool cam_cand_scene(const rs_scene* s, const DScene& d) {
+    return cam_cand(s->scene_mode, kExtCamera) && d.moving == 0 && d.lsphs && d.root4 >= 0 && !d.ref_order &&
+           s->objs.size() <= kCandMaxEntries && s->stack_need <= kCandStack;  // (this mode's leaf codes name handles)
+}
+const uint4* cam_cand_records(const rs_scene* s, const FrameConsts& c, Slot& L, hipStream_t L0) {
+    const PathParams& pp = c.pp;
+    if (!cam_cand_scene(s, *c.ds.host) || pp.n_pix_local == 0 || pp.n_pix_local > (0xFFFFFFFFu >> 4)) return nullptr;
+    if (!cand_camera(c.dc.origin, c.dc.lb, c.dc.hf, c.dc.vf, c.dc.hu, c.dc.vu, c.dc.aperture, pp.width, pp.height).ok)
+        return nullptr;
+    CandKey key;
+    key.dc = c.dc;
+    key.width = pp.width; key.height = pp.height; key.row_begin = pp.row_begin; key.row_step = pp.row_step;
+    key.n_pix = pp.n_pix_local;
+    key.gen = s->commit_gen;
+    key.valid = true;
+    if (L.cand_key.same(key)) return L.d_cand;
+    L.cand_key.valid = false;
+    // (a whole frame's worth at least, so a slot that alternates between a frame and its row shares allocates once)
+    if (!try_ensure(L, L.d_cand, L.cand_cap, std::max<size_t>(pp.n_pix_local, (size_t)pp.width * pp.height))) return nullptr;
+    HIP_OK(launch_cam_cand_build(c.ds, c.dc, pp, L.d_cand, L0));
+    L.cand_key = key;
+    return L.d_cand;
+}
+
 // A streaming frame being enqueued: what its iterations and accumulates share (enqueue_streaming).
 struct StreamFrame {
     const rs_scene* s; const FrameConsts& c; Pending& P; Slot& L;
+    const uint4* cand = nullptr;  // cam_cand_records
     FrameSched f;
     GridHist h;
     bool split, split_shade;
@@ -1922,6 +1980,7 @@ void StreamFrame::iteration(uint32_t l, uint64_t t) {
     const uint32_t n_new = ln.n_new(t);
     P.inj[l][t] = n_new;
     InjParams I = inj_params(f, ln, t);
+    I.cand = cand;
     if (n_new) {
         const uint64_t m = t * ln.Q / f.B;
         // a batch taking over a ring buffer: after the batch `ring` earlier was accumulated
@@ -2034,6 +2093,7 @@ void enqueue_streaming(const rs_scene* s, const rs_render_settings* st, const Fr
     F.h = hist_begin(*P.R, L, f, n_pix, N, D, n_frames);
     // every lane and the accumulate stream start after L0's dependencies and the counter reset
     if (!L.acc_stream) HIP_OK(hipStreamCreateWithFlags(&L.acc_stream, hipStreamNonBlocking));
+    F.cand = cam_cand_records(s, c, L, L0);  // (a new camera's build: on L0, ahead of every lane)
     fork_lanes(L, f.lanes);
     HIP_OK(hipStreamWaitEvent(L.acc_stream, L.fork_ev, 0));
     if (n_frames > 1) HIP_OK(hipStreamWaitEvent(L.acc_stream, c.outs_after, 0));

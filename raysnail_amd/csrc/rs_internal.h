@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "rs_layout.h"
+#include "rs_cam_cand.h"
 
 namespace rs {
 
@@ -135,6 +136,7 @@ struct InjParams {
     uint64_t g0, g1;      // frame items of the two batches' starts (k * batch: a lane's batches are not adjacent)
     uint32_t rad0, rad1;  // rad ring offsets of the two batches' buffers
     uint64_t key0, key1;  // the two batches' PathParams::key_base (a multi-pass stream: their passes' keys)
+    const uint4* cand;    // the lattice pixels' candidate records (cam_cand below; null: the camera rays walk the tree)
 };
 
 struct FinalParams {
@@ -197,6 +199,18 @@ constexpr bool ext_split(int sm) { return sm == kSmNest2 || sm == kSmSpheres; }
 #define RS_CAM_FUSE 1
 #endif
 constexpr bool cam_fused(int sm, int part) { return RS_CAM_FUSE && sm == kSmSpheres && part == kExtCamera; }
+// The spheres mode's camera launch finds a sample's hit among its lattice pixel's candidate spheres (one 16-byte
+// record per pixel, rs_cam_cand.h, written once per camera, lattice and scene by k_cam_cand_build) instead of walking
+// the tree: a pixel's camera rays all leave the lens disk through that pixel's footprint on the focus plane, so what
+// they can touch depends on neither sample, seed nor pass. RS_CAM_CAND=0: the kernel that always walks, for A/B.
+#ifndef RS_CAM_CAND
+#define RS_CAM_CAND 1
+#endif
+constexpr bool cam_cand(int sm, int part) { return RS_CAM_CAND && sm == kSmSpheres && part == kExtCamera; }
+// one record per lattice pixel of p (n_pix_local, width, height, row_begin, row_step) into cand[0, n_pix_local); the
+// scene is a spheres-mode one without motion on the near-first 4-wide tree, stack_need <= kCandStack (the caller's
+// checks: cam_cand_scene in rs_host.cpp)
+hipError_t launch_cam_cand_build(const SceneRef& s, const DCamera& c, const PathParams& p, uint4* cand, hipStream_t st);
 hipError_t launch_wfs_extend(const SceneRef& s, const DCamera& c, const PathParams& p, const WfState& w,
                              QEnt* const* queues, uint32_t it, const InjParams& inj, double* rad, uint32_t blocks,
                              int part, int sm, hipStream_t st, hipEvent_t ev0 = nullptr, hipEvent_t ev1 = nullptr);

@@ -3,6 +3,7 @@
 //   k_path_mega   painter.rs:154-187 (render_pixel, one sample) -> camera.rs:77-85 (Camera::ray)
 //                 -> camera.rs:156-255 (ray_color, iterated) with BVH traversal (bvh.rs:173-192)
 //   k_wfs_extend / k_wfs_shade_all / k_wf_*   the wavefront form of the same recursion
+//   k_cam_cand_build   the spheres a lattice pixel's camera rays can touch (rs_cam_cand.h), for k_wfs_extend's camera part
 //   k_accumulate  painter.rs:167-179 color_vec sum, in sample order; its last batch also does
 //                 vec3.rs:227-240 into_color (/N, sqrt gamma, f32, alpha 1) + painter.rs:204-210 mask
 //   k_finalize    into_color alone (frames without samples)
@@ -362,8 +363,12 @@ __device__ __forceinline__ LTri ld_ltri(const LTri* arr, int i) {
 }
 
 // Sphere leaf (leaf entry e): discriminant first, then the exact own box for spheres that hit.
+// TIE (the camera launch's candidate lists, whose order is not the walk's): a sphere whose t equals the best one is
+// not tested further but reported in *tie -- the range end is the next double above best, so the roots and their
+// order of choice are the ones the range [tmin, best) gives, and t == best is the only new outcome.
+template <bool TIE = false>
 __device__ __forceinline__ void test_sphere_leaf(const DScene& S, const DSphere& sp, int e, const Ray& r, const RayC& rc,
-                                                 double tmin, double& best, double& bend, int& bp) {
+                                                 double tmin, double& best, double& bend, int& bp, bool* tie = nullptr) {
     double t;
 #ifdef RS_LEAF_TWICE  // dev bound (tools/build_variant.sh): the quadratic done twice, the copy's inputs opaque
     {
@@ -374,7 +379,12 @@ __device__ __forceinline__ void test_sphere_leaf(const DScene& S, const DSphere&
         asm volatile("" ::"v"(t2), "v"((int)h2));
     }
 #endif
-    if (!sphere_t_trav(sp, r, rc.a, tmin, best, t, S.moving != 0)) return;
+    double tend = best;
+    if constexpr (TIE)  // best is +inf or a positive finite t (>= tmin > 0), whose bit pattern + 1 is the next double
+        if (best < RS_INF) tend = __longlong_as_double(__double_as_longlong(best) + 1ll);
+    if (!sphere_t_trav(sp, r, rc.a, tmin, tend, t, S.moving != 0)) return;
+    if constexpr (TIE)
+        if (t == best) { *tie = true; return; }
     double lo[3], hi[3];
     if (!S.moving || (sp.v[0] == 0.0 && sp.v[1] == 0.0 && sp.v[2] == 0.0)) {  // host: c -/+ r (sphere.rs:117-124)
         lo[0] = sp.c[0] - sp.r; lo[1] = sp.c[1] - sp.r; lo[2] = sp.c[2] - sp.r;
@@ -1261,9 +1271,11 @@ __device__ __forceinline__ void camera_sample_xy(const DCamera& C, const PathPar
     const double hh = (double)P.height;
     r = camera_ray(C, xo / (double)P.width, (hh - 1.0 - yo) / hh, rng);
 }
+// pl_out (when given): the sample's lattice pixel (the index of its candidate record, rs_cam_cand.h)
 __device__ __forceinline__ bool camera_sample(const DCamera& C, const PathParams& P, uint64_t key, uint64_t item, Ray& r,
-                                              Rng& rng) {
+                                              Rng& rng, uint32_t* pl_out = nullptr) {
     const uint32_t pl = (uint32_t)(item % P.n_pix_local);
+    if (pl_out) *pl_out = pl;
     const uint32_t sl = (uint32_t)(item / P.n_pix_local);
     const uint32_t x = pl % P.width;
     const uint32_t y = P.row_begin + (pl / P.width) * P.row_step;
@@ -1719,6 +1731,8 @@ __global__ __launch_bounds__(kBlock, ext_min_waves(SM, LOBJ, PART)) void k_wfs_e
     const WfSet& cur = W.set[it & 1];
     // the spheres mode's camera launch shades its lean-class hits in place (below)
     constexpr bool kFuse = cam_fused(SM, PART);
+    // ... and finds them among the pixel's candidate spheres where the launch has the records (below)
+    constexpr bool kCand = cam_cand(SM, PART);
     const uint32_t base0 = blockIdx.x * kBlock;
     for (uint32_t base = base0; base < n; base += gridDim.x * kBlock) {
         // thread -> record: the front run [0, nf), the back run from the set's end down, then the
@@ -1733,11 +1747,12 @@ __global__ __launch_bounds__(kBlock, ext_min_waves(SM, LOBJ, PART)) void k_wfs_e
         Ray r;
         Rng rng;
         uint32_t item = 0;
+        [[maybe_unused]] uint32_t pl = 0;  // kCand: the camera sample's lattice pixel
         if (j < n) {
             if (gen) {
                 uint64_t g, key;
                 inj_sample(I, P, j - n_old, g, key, item);
-                live = camera_sample(C, P, key, g, r, rng);
+                live = camera_sample(C, P, key, g, r, rng, kCand ? &pl : nullptr);
                 if (!live) put_rad(rad, item, 0.0, 0.0, 0.0);
             } else {
                 r = load_ray(cur, i, W.tagw);
@@ -1759,7 +1774,41 @@ __global__ __launch_bounds__(kBlock, ext_min_waves(SM, LOBJ, PART)) void k_wfs_e
             double bend = RS_INF;
             // the spheres mode keeps the winner's t (the queue entry: the shading's sphere_rec_at), the others the range end
             constexpr bool kT = SM == kSmSpheres;
-            const int bp = traverse<SM, StkT<OVF, stack_lds(SM)>, LOBJ, kT, kTop>(S, r, 0.0001, bend, stk);
+            int bp = -1;
+            bool walk = true;
+            // The pixel's candidate list in place of the walk: the pixel's record (16 B, a wave reads its two pixels'),
+            // then the walk's own leaf test on each entry in list order. Closest hit among spheres does not depend on
+            // the order except where two spheres share the best t exactly, which the walk
+            // resolves by its order: such a lane walks, as do the lanes of an overflow pixel (more than kCandMax
+            // candidates) and every lane of a launch without records. Scenes with lists have no moving sphere.
+            if constexpr (kCand) {
+                if (I.cand) {
+                    const i4v rv = gld<i4v>(I.cand, pl * 16u);
+                    uint4 rec = make_uint4((uint32_t)rv.x, (uint32_t)rv.y, (uint32_t)rv.z, (uint32_t)rv.w);
+                    if ((rec.x & 0xFFFFu) != kCandOverflow) {
+                        const RayC rc = ray_consts(r);
+                        double best = RS_INF, be = RS_INF;
+                        bool tie = false;
+                        TravStat st;
+                        // one copy of the leaf test; the record is shifted down an entry per pass (empty ones come in)
+                        for (uint32_t k = 0; k < kCandMax; ++k) {
+                            const uint32_t e = rec.x & 0xFFFFu;
+                            if (e == kCandEmpty) break;
+                            rec.x = (rec.x >> 16) | (rec.y << 16); rec.y = (rec.y >> 16) | (rec.z << 16);
+                            rec.z = (rec.z >> 16) | (rec.w << 16); rec.w = (rec.w >> 16) | 0xFFFF0000u;
+                            st.leaf();
+                            test_sphere_leaf<true>(S, ld_sphere_s(S.lsphs, (int)e), (int)e, r, rc, 0.0001, best, be, bp, &tie);
+                        }
+                        if (!tie) {
+                            walk = false;
+                            st.store();
+                            bend = best;  // kT: the winner's t
+                            if (bp >= 0 && S.lprim) bp = S.lprim[bp];
+                        }
+                    }
+                }
+            }
+            if (walk) bp = traverse<SM, StkT<OVF, stack_lds(SM)>, LOBJ, kT, kTop>(S, r, 0.0001, bend, stk);
             V3 add;
             bool done = true;
             if (bp < 0) {  // sky miss: L + T * background (camera.rs:253-254)
@@ -2593,6 +2642,71 @@ hipError_t launch_features(const SceneRef& s, const DCamera& c, const PathParams
 }
 #endif
 #endif  // the feature unit or the marcher unit
+
+#if !defined(RS_TU) || RS_TU == 1
+// The candidate records of the spheres mode's camera launch (rs_cam_cand.h; cam_cand in rs_internal.h): one thread
+// per lattice pixel walks the 4-wide tree with the pixel's beam against each child box's bounding sphere, tests the
+// sphere of every leaf it reaches with the same criterion and writes the pixel's 16-byte record, nearest first along
+// the beam's axis. The walk continues into the first inner child that passes and pushes the others, as traverse()'s
+// near-first walk does, so it needs at most the tree's stack_need entries (the host gives a scene lists only when
+// that fits kCandStack; a push beyond it marks the pixel overflow instead of writing). Once per camera, lattice and
+// scene: nothing here is hot.
+__global__ __launch_bounds__(kBlock) void k_cam_cand_build(const DScene* __restrict__ Sp, DCamera C, PathParams P,
+                                                           uint4* __restrict__ cand) {
+    const uint32_t pl = blockIdx.x * kBlock + threadIdx.x;
+    if (pl >= P.n_pix_local) return;
+    const DScene& S = *Sp;
+    const uint32_t x = pl % P.width, y = P.row_begin + (pl / P.width) * P.row_step;
+    const CandCam cc = cand_camera(C.origin, C.lb, C.hf, C.vf, C.hu, C.vu, C.aperture, P.width, P.height);
+    const CandBeam b = cand_beam(cc, x, y);
+    CandList l;
+    cand_list_init(l);
+    if (!b.ok || S.root4 < 0) {
+        l.n = kCandMax + 1;  // no beam for this pixel: its rays walk
+    } else {
+        int stk[kCandStack];
+        int sp = 0, node = S.root4;
+        while (node >= 0 && !cand_list_overflow(l)) {
+            const DNode4& N = S.nodes4[node];
+            int next = -1;
+            for (int k = 0; k < 4; ++k) {
+                const int c = N.child[k];
+                if (c == INT32_MIN) continue;
+                // the box's bounding sphere, the half diagonal rounded up
+                const double lo[3] = {(double)N.lo_x[k], (double)N.lo_y[k], (double)N.lo_z[k]};
+                const double hi[3] = {(double)N.hi_x[k], (double)N.hi_y[k], (double)N.hi_z[k]};
+                const double ctr[3] = {0.5 * (lo[0] + hi[0]), 0.5 * (lo[1] + hi[1]), 0.5 * (lo[2] + hi[2])};
+                const double ex = hi[0] - lo[0], ey = hi[1] - lo[1], ez = hi[2] - lo[2];
+                const double rad = 0.5 * sqrt(ex * ex + ey * ey + ez * ez) * (1.0 + 0x1p-40);
+                if (!cand_sphere(b, ctr, rad)) continue;
+                if (c < 0) {
+                    const DSphere sp_ = ld_sphere_s(S.lsphs, ~c);
+                    double along;
+                    if (cand_sphere(b, sp_.c, sp_.r, &along)) cand_list_add(l, (uint32_t)~c, along);
+                } else if (next < 0) {
+                    next = c;
+                } else if (sp < kCandStack) {
+                    stk[sp++] = c;
+                } else {
+                    l.n = kCandMax + 1;
+                }
+            }
+            if (next < 0 && sp > 0) next = stk[--sp];
+            node = next;
+        }
+    }
+    uint32_t w[4];
+    cand_list_pack(l, w);
+    cand[pl] = make_uint4(w[0], w[1], w[2], w[3]);
+}
+
+hipError_t launch_cam_cand_build(const SceneRef& s, const DCamera& c, const PathParams& p, uint4* cand, hipStream_t st) {
+    const uint32_t blocks = (p.n_pix_local + kBlock - 1) / kBlock;
+    if (!blocks) return hipSuccess;
+    hipLaunchKernelGGL(k_cam_cand_build, dim3(blocks), dim3(kBlock), 0, st, s.dev, c, p, cand);
+    return hipGetLastError();
+}
+#endif  // the spheres unit
 
 // ---- launchers ----
 // Mode-dependent launchers: launch_X_sm<SM> (defined and instantiated per mode unit) behind a

@@ -1,0 +1,298 @@
+// The candidate criterion of the spheres mode's camera launch (raysnail_amd/csrc/rs_cam_cand.h) on the CPU.
+//
+// A restatement of the list build with the shared criterion, by brute force over all spheres (a superset of what the
+// GPU's tree walk finds: the walk only culls with the same function on node boxes), checked against rays drawn from
+// the exact family camera_ray / camera_sample_xy produce: for a fixed set of about 200 pixels per camera, 4,096
+// rays per pixel -- lens points on the disk's rim and inside it, footprint points at all four corners, on both
+// inclusive ends and inside -- are intersected with every sphere by the exact f64 test (sphere.rs:83-109 over
+// [0.0001, inf)), and every sphere that is hit must be in the pixel's packed record unless the record is marked
+// overflow. Cameras: the bench camera at 96 x 60 over an RTIOW-shaped scene (and over the spheres of a file given
+// as argv[1]: "cx cy cz r" per line), a wide lens (aperture 2, focus 4, spheres 0.5 - 3 units from the lens), a
+// pinhole, and a camera inside a large sphere. For the bench camera at most 6 % of the pixels with any candidate may
+// be marked overflow, so that the property cannot pass by overflowing everywhere.
+//
+// Stand-alone (no library): g++ -O2 -std=c++17 tests/cpp/test_cam_cand.cpp; prints "ok" last and exits 0.
+#include <cmath>
+#include <cstdint>
+#include <cstdio>
+#include <cstdlib>
+#include <limits>
+#include <vector>
+
+#include "../../raysnail_amd/csrc/rs_cam_cand.h"
+
+using namespace rs;
+
+struct Sph { double c[3], r; };
+struct Cam {
+    double origin[3], lb[3], hf[3], vf[3], hu[3], vu[3], aperture;
+    uint32_t W, H;
+};
+
+static uint64_t g_rng = 0x9E3779B97F4A7C15ull;
+static double rnd() {  // [0, 1)
+    g_rng ^= g_rng << 13; g_rng ^= g_rng >> 7; g_rng ^= g_rng << 17;
+    return (double)(g_rng >> 11) * 0x1p-53;
+}
+
+// camera.rs:37-73 as the library's make_camera states it (aspect = width / height)
+static Cam make_cam(const double from[3], const double at[3], double fov, double aperture, double focus, uint32_t W, uint32_t H) {
+    const double vup[3] = {0.0, 1.0, 0.0};
+    auto unit = [](const double* a, double* o) {
+        const double inv = 1.0 / std::sqrt(a[0] * a[0] + a[1] * a[1] + a[2] * a[2]);
+        for (int i = 0; i < 3; ++i) o[i] = a[i] * inv;
+    };
+    auto cross = [](const double* a, const double* b, double* o) {
+        const double r[3] = {a[1] * b[2] - a[2] * b[1], a[2] * b[0] - a[0] * b[2], a[0] * b[1] - a[1] * b[0]};
+        o[0] = r[0]; o[1] = r[1]; o[2] = r[2];
+    };
+    const double h = std::tan(fov * (3.14159265358979323846 / 180.0) / 2.0);
+    const double vh = 2.0 * h * focus, vw = vh * ((double)W / (double)H);
+    double d[3] = {at[0] - from[0], at[1] - from[1], at[2] - from[2]}, w[3], t[3];
+    Cam c;
+    unit(d, w);
+    cross(w, vup, t); unit(t, c.hu);
+    cross(c.hu, w, t); unit(t, c.vu);
+    for (int i = 0; i < 3; ++i) {
+        c.origin[i] = from[i];
+        c.hf[i] = c.hu[i] * vw;
+        c.vf[i] = c.vu[i] * vh;
+    }
+    for (int i = 0; i < 3; ++i) c.lb[i] = from[i] - c.hf[i] * 0.5 - c.vf[i] * 0.5 + w[i] * focus;
+    c.aperture = aperture;
+    c.W = W; c.H = H;
+    return c;
+}
+
+// camera_ray (rs_device.h) for a lens point `disk` (|disk| < 1) and a footprint point (u, v)
+static void cam_ray(const Cam& c, const double disk[2], double u, double v, double o[3], double d[3]) {
+    const double rdx = (c.aperture / 2.0) * disk[0], rdy = (c.aperture / 2.0) * disk[1];
+    double dir[3];
+    for (int i = 0; i < 3; ++i) {
+        const double off = c.hu[i] * rdx + c.vu[i] * rdy;
+        o[i] = c.origin[i] + off;
+        dir[i] = c.lb[i] + u * c.hf[i] + v * c.vf[i] - o[i];
+    }
+    const double l = std::sqrt(dir[0] * dir[0] + dir[1] * dir[1] + dir[2] * dir[2]);
+    for (int i = 0; i < 3; ++i) d[i] = dir[i] / l;
+}
+
+// Sphere::hit over [tmin, inf) (sphere.rs:83-109): is there a root in range?
+static bool sphere_hit(const Sph& s, const double o[3], const double d[3], double tmin) {
+    const double l[3] = {o[0] - s.c[0], o[1] - s.c[1], o[2] - s.c[2]};
+    const double a = d[0] * d[0] + d[1] * d[1] + d[2] * d[2];
+    const double half_b = d[0] * l[0] + d[1] * l[1] + d[2] * l[2];
+    const double cc = l[0] * l[0] + l[1] * l[1] + l[2] * l[2] - s.r * s.r;
+    const double delta = half_b * half_b - a * cc;
+    if (delta < 0.0) return false;
+    const double sq = std::sqrt(delta);
+    return (-half_b - sq) / a >= tmin || (-half_b + sq) / a >= tmin;
+}
+
+struct Record { uint32_t e[kCandMax]; uint32_t n; bool overflow; };
+static Record build_record(const CandCam& cc, const std::vector<Sph>& sph, uint32_t x, uint32_t y) {
+    const CandBeam b = cand_beam(cc, x, y);
+    CandList l;
+    cand_list_init(l);
+    if (!b.ok) l.n = kCandMax + 1;
+    for (size_t i = 0; i < sph.size() && !cand_list_overflow(l); ++i) {
+        double along;
+        if (cand_sphere(b, sph[i].c, sph[i].r, &along)) cand_list_add(l, (uint32_t)i, along);
+    }
+    uint32_t w[4];
+    cand_list_pack(l, w);
+    Record r;
+    r.n = 0;
+    r.overflow = (w[0] & 0xFFFFu) == kCandOverflow;
+    for (uint32_t k = 0; k < kCandMax && !r.overflow; ++k) {
+        const uint32_t e = (w[k / 2] >> (16 * (k & 1))) & 0xFFFFu;
+        if (e == kCandEmpty) break;
+        r.e[r.n++] = e;
+    }
+    return r;
+}
+
+static int g_fail = 0;
+#define CHECK(cond, ...)                                     \
+    do {                                                     \
+        if (!(cond)) {                                       \
+            if (g_fail < 20) { std::printf("FAIL %s:%d: ", __FILE__, __LINE__); std::printf(__VA_ARGS__); std::printf("\n"); } \
+            ++g_fail;                                        \
+        }                                                    \
+    } while (0)
+
+// the pixels of a camera: corners, edge midpoints and quarter points, and a seeded sample, about 200 in all
+static std::vector<std::pair<uint32_t, uint32_t>> pick_pixels(uint32_t W, uint32_t H) {
+    std::vector<std::pair<uint32_t, uint32_t>> px;
+    const uint32_t xs[5] = {0, W / 4, W / 2, 3 * W / 4, W - 1}, ys[5] = {0, H / 4, H / 2, 3 * H / 4, H - 1};
+    for (uint32_t x : xs) for (uint32_t y : ys) px.push_back({x, y});
+    while (px.size() < 200) px.push_back({(uint32_t)(rnd() * W) % W, (uint32_t)(rnd() * H) % H});
+    return px;
+}
+
+// Every sphere hit by a ray of a pixel's family is in the pixel's record (or the record overflows). cap: the share of
+// the pixels with any candidate that may overflow, over the whole frame (negative: not checked).
+static void check_camera(const char* name, const Cam& c, const std::vector<Sph>& sph, double cap) {
+    const CandCam cc = cand_camera(c.origin, c.lb, c.hf, c.vf, c.hu, c.vu, c.aperture, c.W, c.H);
+    CHECK(cc.ok, "%s: camera not usable", name);
+    if (!cc.ok) return;
+    CHECK(sph.size() <= kCandMaxEntries, "%s: too many spheres for a record", name);
+    // the frame's statistics
+    uint64_t with = 0, over = 0, sum = 0, mx = 0;
+    for (uint32_t y = 0; y < c.H; ++y)
+        for (uint32_t x = 0; x < c.W; ++x) {
+            const Record r = build_record(cc, sph, x, y);
+            if (r.overflow) { ++with; ++over; continue; }
+            if (r.n) ++with;
+            sum += r.n;
+            if (r.n > mx) mx = r.n;
+        }
+    const double share = with ? (double)over / (double)with : 0.0;
+    std::printf("%-14s %ux%u, %zu spheres: mean %.3f candidates per pixel (without overflow pixels), max %llu, overflow %.2f %% of %llu pixels with candidates\n",
+                name, c.W, c.H, sph.size(), (double)sum / (double)((uint64_t)c.W * c.H - over ? (uint64_t)c.W * c.H - over : 1),
+                (unsigned long long)mx, 100.0 * share, (unsigned long long)with);
+    if (cap >= 0.0) CHECK(share <= cap, "%s: %.2f %% of the pixels with candidates overflow (cap %.2f %%)", name, 100.0 * share, 100.0 * cap);
+
+    const double W = (double)c.W, H = (double)c.H;
+    uint64_t rays = 0, hits = 0, missed = 0, over_px = 0;
+    for (const auto& p : pick_pixels(c.W, c.H)) {
+        const uint32_t x = p.first, y = p.second;
+        const Record r = build_record(cc, sph, x, y);
+        if (r.overflow) { ++over_px; continue; }  // such a pixel's rays walk the tree
+        // the footprint's inclusive ends as camera_sample_xy reaches them: xo in [x, x + 1], yo in [y, y + 1]
+        const double u0 = (double)x / W, u1 = ((double)x + 1.0) / W;
+        const double v0 = (H - 1.0 - ((double)y + 1.0)) / H, v1 = (H - 1.0 - (double)y) / H;
+        for (int k = 0; k < 4096; ++k) {
+            double disk[2], u, v;
+            // lens: a quarter on the rim (as close to it as |p|^2 < 1 allows), the rest inside; the first 8 rays
+            // pair the footprint's corners with two opposite rim points
+            const double ang = k < 8 ? (k & 4 ? 3.14159265358979323846 : 0.0) + 0.3 : rnd() * 6.283185307179586;
+            const double rad = (k < 8 || (k & 3) == 0) ? 1.0 - 0x1p-50 : std::sqrt(rnd());
+            disk[0] = rad * std::cos(ang); disk[1] = rad * std::sin(ang);
+            if (disk[0] * disk[0] + disk[1] * disk[1] >= 1.0) { disk[0] *= 1.0 - 0x1p-40; disk[1] *= 1.0 - 0x1p-40; }
+            if (k < 8) { u = (k & 1) ? u1 : u0; v = (k & 2) ? v1 : v0; }
+            else if ((k & 7) == 1) { u = rnd() < 0.5 ? u0 : u1; v = v0 + (v1 - v0) * rnd(); }   // an inclusive end in u
+            else if ((k & 7) == 2) { v = rnd() < 0.5 ? v0 : v1; u = u0 + (u1 - u0) * rnd(); }   // ... in v
+            else {
+                const double xo = (double)x + rnd(), yo = (double)y + rnd();
+                u = xo / W; v = (H - 1.0 - yo) / H;
+            }
+            double o[3], d[3];
+            cam_ray(c, disk, u, v, o, d);
+            ++rays;
+            for (size_t i = 0; i < sph.size(); ++i) {
+                if (!sphere_hit(sph[i], o, d, 0.0001)) continue;
+                ++hits;
+                bool in = false;
+                for (uint32_t q = 0; q < r.n; ++q) in = in || r.e[q] == (uint32_t)i;
+                if (!in) ++missed;
+                CHECK(in, "%s: pixel (%u, %u) ray %d hits sphere %zu (c %.17g %.17g %.17g r %.17g), not in its record of %u",
+                      name, x, y, k, i, sph[i].c[0], sph[i].c[1], sph[i].c[2], sph[i].r, r.n);
+            }
+        }
+    }
+    std::printf("%-14s %llu rays, %llu sphere hits, %llu not listed; %llu of the picked pixels overflow\n", name,
+                (unsigned long long)rays, (unsigned long long)hits, (unsigned long long)missed, (unsigned long long)over_px);
+    CHECK(rays > 0, "%s: every picked pixel overflows", name);
+}
+
+// the layout of RTIOW-13.1 (examples/common/scene.rs): ground, a 22 x 22 field of small spheres, three large ones, the light
+static std::vector<Sph> rtiow_like() {
+    std::vector<Sph> s;
+    s.push_back({{0.0, -1000.0, 0.0}, 1000.0});
+    for (int a = -11; a < 11; ++a)
+        for (int b = -11; b < 11; ++b) {
+            const Sph q = {{a + 0.9 * rnd(), 0.2, b + 0.9 * rnd()}, 0.2};
+            const double dx = q.c[0] - 4.0, dz = q.c[2];
+            if (std::sqrt(dx * dx + dz * dz) > 0.9) s.push_back(q);
+        }
+    s.push_back({{0.0, 1.0, 0.0}, 1.0});
+    s.push_back({{-4.0, 1.0, 0.0}, 1.0});
+    s.push_back({{4.0, 1.0, 0.0}, 1.0});
+    s.push_back({{300.0, 400.0, 100.0}, 12.0});
+    return s;
+}
+
+int main(int argc, char** argv) {
+    const double from[3] = {13.0, 2.0, 3.0}, at[3] = {0.0, 0.0, 0.0};
+    const Cam bench = make_cam(from, at, 20.0, 0.02, 10.0, 96, 60);
+    if (argc > 1) {  // the scene's own spheres
+        std::vector<Sph> s;
+        std::FILE* f = std::fopen(argv[1], "r");
+        if (!f) { std::printf("cannot open %s\n", argv[1]); return 2; }
+        Sph q;
+        while (std::fscanf(f, "%lf %lf %lf %lf", &q.c[0], &q.c[1], &q.c[2], &q.r) == 4) s.push_back(q);
+        std::fclose(f);
+        CHECK(!s.empty(), "no spheres in %s", argv[1]);
+        check_camera("bench (file)", bench, s, 0.06);
+    }
+    const std::vector<Sph> field = rtiow_like();
+    check_camera("bench", bench, field, 0.06);
+    {
+        // a wide lens in front of a cloud of spheres 0.5 - 3 units away
+        const double f0[3] = {0.0, 0.0, 0.0}, a0[3] = {0.0, 0.0, -1.0};
+        const Cam wide = make_cam(f0, a0, 40.0, 2.0, 4.0, 64, 40);
+        std::vector<Sph> s;
+        for (int i = 0; i < 16; ++i) {
+            const double r = 0.1 + 0.2 * rnd(), dist = 0.5 + 2.5 * rnd() + r;
+            const double th = (rnd() - 0.5) * 2.4, ph = (rnd() - 0.5) * 1.6;
+            s.push_back({{dist * std::sin(th), dist * std::sin(ph), -dist * std::cos(th) * std::cos(ph)}, r});
+        }
+        s.push_back({{0.0, -1003.0, 0.0}, 1000.0});
+        check_camera("wide lens", wide, s, -1.0);
+    }
+    check_camera("pinhole", make_cam(from, at, 20.0, 0.0, 10.0, 64, 40), field, -1.0);
+    {
+        // the camera inside a large sphere, smaller ones inside and outside it
+        const double f0[3] = {1.0, 0.5, 2.0}, a0[3] = {0.0, 0.0, -3.0};
+        const Cam in = make_cam(f0, a0, 50.0, 0.1, 5.0, 64, 40);
+        std::vector<Sph> s;
+        s.push_back({{0.0, 0.0, 0.0}, 50.0});
+        s.push_back({{1.0, 0.5, 2.0}, 0.3});   // around the lens itself
+        for (int i = 0; i < 30; ++i) s.push_back({{(rnd() - 0.5) * 12.0, (rnd() - 0.5) * 8.0, -3.0 - 20.0 * rnd()}, 0.3 + rnd()});
+        for (int i = 0; i < 10; ++i) s.push_back({{(rnd() - 0.5) * 80.0, (rnd() - 0.5) * 60.0, -70.0 - 40.0 * rnd()}, 2.0 + 3.0 * rnd()});
+        check_camera("inside sphere", in, s, -1.0);
+    }
+    {
+        // degenerate data: no lists
+        Cam c = bench;
+        const double nan = std::numeric_limits<double>::quiet_NaN(), inf = std::numeric_limits<double>::infinity();
+        CHECK(!cand_camera(c.origin, c.lb, c.hf, c.vf, c.hu, c.vu, c.aperture, 0, 60).ok, "width 0 accepted");
+        CHECK(!cand_camera(c.origin, c.lb, c.hf, c.vf, c.hu, c.vu, c.aperture, 96, 0).ok, "height 0 accepted");
+        CHECK(!cand_camera(c.origin, c.lb, c.hf, c.vf, c.hu, c.vu, nan, 96, 60).ok, "NaN aperture accepted");
+        c.hf[1] = nan;
+        CHECK(!cand_camera(c.origin, c.lb, c.hf, c.vf, c.hu, c.vu, c.aperture, 96, 60).ok, "NaN hf accepted");
+        c = bench; c.origin[2] = inf;
+        CHECK(!cand_camera(c.origin, c.lb, c.hf, c.vf, c.hu, c.vu, c.aperture, 96, 60).ok, "inf origin accepted");
+        // F == O: the beam of that pixel is unusable, the criterion keeps everything and the record overflows
+        c = bench;
+        for (int i = 0; i < 3; ++i) { c.hf[i] = 0.0; c.vf[i] = 0.0; c.lb[i] = c.origin[i]; }
+        const CandCam cc = cand_camera(c.origin, c.lb, c.hf, c.vf, c.hu, c.vu, c.aperture, 96, 60);
+        const CandBeam b = cand_beam(cc, 3, 4);
+        CHECK(!b.ok, "F == O gives a beam");
+        const double far_c[3] = {1e6, 1e6, 1e6};
+        CHECK(cand_sphere(b, far_c, 1.0), "an unusable beam rejects a sphere");
+        CHECK(build_record(cc, field, 3, 4).overflow, "F == O: the record is not marked overflow");
+        // a NaN sphere is kept
+        const CandBeam ok = cand_beam(cand_camera(bench.origin, bench.lb, bench.hf, bench.vf, bench.hu, bench.vu, bench.aperture, 96, 60), 10, 10);
+        const double nan_c[3] = {nan, 0.0, 0.0};
+        CHECK(cand_sphere(ok, nan_c, 1.0), "a NaN centre is rejected");
+        CHECK(!cand_sphere(ok, far_c, 1.0), "a sphere far off the beam is kept");
+    }
+    // the record's packing: order, empties, overflow
+    {
+        CandList l;
+        cand_list_init(l);
+        cand_list_add(l, 7, 3.0); cand_list_add(l, 9, 1.0); cand_list_add(l, 2, 2.0);
+        uint32_t w[4];
+        cand_list_pack(l, w);
+        CHECK(w[0] == (9u | (2u << 16)) && w[1] == (7u | (0xFFFFu << 16)) && w[2] == 0xFFFFFFFFu && w[3] == 0xFFFFFFFFu, "pack order");
+        for (uint32_t i = 0; i < 6; ++i) cand_list_add(l, 100 + i, 10.0 + i);
+        CHECK(cand_list_overflow(l), "nine candidates do not overflow");
+        cand_list_pack(l, w);
+        CHECK((w[0] & 0xFFFFu) == kCandOverflow, "overflow mark");
+    }
+    if (g_fail) { std::printf("%d checks failed\n", g_fail); return 1; }
+    std::printf("ok\n");
+    return 0;
+}
