@@ -547,6 +547,15 @@ void denoise(std::vector<Pixel>& pixels, const std::vector<Pixel>* albedo, const
 // radiance over the n frames that contribute to the pixel. gamma: the frames carry the sqrt gamma.
 struct PassMoments { std::vector<Pixel> mean, var; };
 PassMoments pass_moments(const std::vector<std::vector<Pixel>>& frames, int W, int H, bool gamma = true);
+// rs_pass_robust over the same frames: pass_moments with the `trimmed` lowest and highest frames of each pixel (ordered
+// by r + g + b) cut from the mean and Winsorised in the variance. trim: the share cut at each end, in [0, 0.5], or
+// ROBUST_AUTO for the Gini-driven trim; anything else throws Error RS_E_INVALID. mean and var are pass_moments' pair
+// (denoise_var consumes them unchanged); trimmed: W * H counts, the frames cut at each end.
+constexpr float ROBUST_AUTO = RS_ROBUST_TRIM_AUTO;
+constexpr float ROBUST_OFF = -2.0f;  // shot_denoised_passes' default: pass_moments, no trimming
+struct PassRobust { std::vector<Pixel> mean, var; std::vector<uint8_t> trimmed; };
+PassRobust pass_robust(const std::vector<std::vector<Pixel>>& frames, int W, int H, bool gamma = true,
+                       float trim = ROBUST_AUTO);
 // rs_denoise_var's knobs (denoise's filter with the colour weight normalised by the local variance); the defaults are
 // the header's
 struct DenoiseVarSettings {
@@ -600,11 +609,12 @@ public:
     // `passes` (>= 2, or Error RS_E_INVALID) progressive passes of the photo -- pass indices pass_index ..
     // pass_index + passes - 1, `samples` each, every frame what shot gives for that pass -- and the first pass's
     // feature frames (shot_features' max_specular = guide_specular); then pass_moments() and denoise_var() with the
-    // photo's gamma. last_stats() is the last pass's.
+    // photo's gamma. last_stats() is the last pass's. robust: ROBUST_OFF = pass_moments(); ROBUST_AUTO or a trim in
+    // [0, 0.5] = pass_robust() in its place; anything else throws Error RS_E_INVALID before anything renders.
     struct DenoisedPasses { std::vector<Pixel> denoised, mean, var; };
     DenoisedPasses shot_denoised_passes(World& world, size_t passes, const PixelController* pixel_map = nullptr,
                                         const DenoiseVarSettings& settings = DenoiseVarSettings(),
-                                        uint32_t guide_specular = 0);
+                                        uint32_t guide_specular = 0, float robust = ROBUST_OFF);
     // The adaptive pass loop from an empty image (rs_render_adaptive): passes pass_index, pass_index + 1, ... of
     // `samples` each, every one rendered only where the running variance estimate (or min_passes) still asks for
     // samples, pixel_map as the base mask. mean: the photo (gamma as set); var = [var_r, var_g, var_b, n] in linear

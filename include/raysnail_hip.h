@@ -531,6 +531,53 @@ int rs_pass_moments_device(const float* const* d_frames, uint32_t n_frames, uint
 int rs_pass_moments(const float* const* frames, uint32_t n_frames, uint32_t width, uint32_t height,
                     int32_t gamma, float* mean, float* var);
 
+/* ---- robust pass combine: per-pixel rank-trimmed mean of K pass frames, and the Winsorised variance of that mean
+ * (median of means, Jung et al. 2015; the trim from the Gini coefficient, Buisine et al. 2021; the variance of a
+ * trimmed mean, Tukey & McLaughlin 1963; no reference counterpart) ----
+ * rs_pass_moments with the t lowest and the t highest frames of each pixel cut: a firefly (one pass frame that caught
+ * a caustic path into a small light) no longer reaches the mean, nor blows up the variance rs_denoise_var divides by.
+ * Frames, outputs and conventions are rs_pass_moments'; the two output frames are consumed by rs_denoise_var unchanged.
+ * RS_E_INVALID before anything touches the device: everything rs_pass_moments refuses (mean and var both NULL too;
+ * trimmed may be NULL: not written); a trim that is neither RS_ROBUST_TRIM_AUTO nor finite in [0, 0.5].
+ *
+ * Arithmetic: rs_pass_moments' rules (all f32, every operation rounded once, IEEE division and square root, no
+ * contraction, no transcendental function). Per pixel p, with F_k = frame k's pixel p, k = 0 .. n_frames-1:
+ *   x_k = F_k.rgb; gamma == 1: x_k = x_k x_k per channel.   Key: s_k = (x_k.r + x_k.g) + x_k.b
+ *   frame k contributes when F_k.a != 0, F_k.rgb are finite and s_k is finite (a square that overflows drops the
+ *   frame: the one difference from rs_pass_moments);   n = the number of contributing frames
+ *   order: frame j is before frame k when s_j < s_k, or s_j == s_k and j < k (a total order; -0.0 == +0.0);
+ *   r_k = the number of contributing j before k
+ *   t_max = (n - 2) / 2 (integer division) for n >= 2, else 0: two frames always survive, the variance stays defined
+ *   trim given:  t = min(t_max, (uint32)floorf(trim (float)n))
+ *   trim == RS_ROBUST_TRIM_AUTO: the Gini coefficient of the keys decides.
+ *     S_s = the sum of s_k over the contributing k in frame order, from +0.0
+ *     N_g = the sum of (float)(2 r_k - (n - 1)) s_k in the same order, from +0.0 (the integer is exact; the product
+ *           rounded, then the addition)
+ *     G = S_s > 0 ? N_g / ((float)n S_s) : 0, then fminf(fmaxf(G, 0), 1) (a NaN becomes 0)
+ *     t = min(t_max, (uint32)floorf((G (float)n) 0.5f))
+ *   h = n - 2 t; frame k is kept when t <= r_k <= n - 1 - t; lo, hi = the frames of rank t and n - 1 - t
+ *   S = the sum of x_k over the kept k in frame order, per channel, from +0.0;   mu = S / (float)h
+ *   w_k = x_lo for r_k < t, x_hi for r_k > n - 1 - t (the whole rgb triple of that frame: the colour stays one some
+ *         pass rendered), else x_k
+ *   mw = (the sum of w_k over the contributing k in frame order, from +0.0) / (float)n
+ *   Q = the sum of (w_k - mw)(w_k - mw) in frame order, from +0.0 (the difference rounded, then its square, then the
+ *       addition);   v = Q / ((float)h (float)(h - 1)) for n >= 2, else +0.0
+ *   mean[p] = rs_pass_moments' mean[p] with this mu;   var[p] = [v_r, v_g, v_b, (float)n];
+ *   trimmed[p] = (uint8)t (0 for n = 0)
+ * At t = 0 every operation is rs_pass_moments', in its order: trim = 0 gives rs_pass_moments' two frames bit for bit
+ * on every pixel none of whose squares overflow.
+ *
+ * rs_pass_robust_device: rs_pass_moments_device's rules (d_frames a HOST array of device pointers that travel in the
+ * argument block; one launch on `stream`, never synchronises, allocates nothing). Every load of a thread comes before
+ * its stores: d_mean may alias a frame. d_var and d_trimmed (W H bytes) overlap nothing.
+ * rs_pass_robust: host buffers; uploads, runs the device variant on the default stream, synchronises, downloads (mean
+ * may be one of the frames). Additive extension of ABI 6. */
+#define RS_ROBUST_TRIM_AUTO ((float)-1.0)
+int rs_pass_robust_device(const float* const* d_frames, uint32_t n_frames, uint32_t width, uint32_t height,
+                          int32_t gamma, float trim, float* d_mean, float* d_var, uint8_t* d_trimmed, void* stream);
+int rs_pass_robust(const float* const* frames, uint32_t n_frames, uint32_t width, uint32_t height,
+                   int32_t gamma, float trim, float* mean, float* var, uint8_t* trimmed);
+
 /* ---- variance-guided denoiser: rs_denoise's a-trous filter with the colour edge-stopping weight normalised by a
  * per-pixel variance that is itself filtered level by level (Schied et al. 2017, SVGF's spatial filter without its
  * temporal half; no reference counterpart) ----

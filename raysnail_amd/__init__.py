@@ -11,6 +11,6 @@ from .api import (AARect, AARectMetrics, Box, Camera, CameraBuilder, Checker, Co
                   Lambertian, MixedMaterial, Metal, PainterController, PainterTarget, PixelController, Point3,
                   Quadric, RaysnailError, Sphere, TakePhotoSettings, TfFacade, Transform, TransformStack,
                   TriangleMesh, Vec3, World, denoise, denoise_device, denoise_var, denoise_var_device, pass_moments,
-                  pass_moments_device, realize)
+                  pass_moments_device, pass_robust, pass_robust_device, realize)
 
 __all__ = [n for n in dir() if not n.startswith("_")]

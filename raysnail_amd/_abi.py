@@ -61,6 +61,7 @@ RS_DENOISE_SIGMA_DEPTH = 0.1
 RS_DENOISE_VAR_LEVELS = 5
 RS_DENOISE_VAR_K_COLOR = 2.5
 RS_DENOISE_VAR_EPS = 1e-6
+RS_ROBUST_TRIM_AUTO = -1.0
 # the adaptive pass loop's (include/raysnail_adaptive.h RS_ADAPTIVE_*)
 RS_ADAPTIVE_MIN_PASSES = 2
 RS_ADAPTIVE_MAX_PASSES = 32
@@ -218,6 +219,11 @@ def load() -> C.CDLL:
     lib.rs_pass_moments_device.restype = C.c_int
     lib.rs_pass_moments.argtypes = [C.POINTER(VP), C.c_uint32, C.c_uint32, C.c_uint32, C.c_int32, VP, VP]
     lib.rs_pass_moments.restype = C.c_int
+    lib.rs_pass_robust_device.argtypes = [C.POINTER(VP), C.c_uint32, C.c_uint32, C.c_uint32, C.c_int32, C.c_float, VP, VP,
+                                          VP, VP]
+    lib.rs_pass_robust_device.restype = C.c_int
+    lib.rs_pass_robust.argtypes = [C.POINTER(VP), C.c_uint32, C.c_uint32, C.c_uint32, C.c_int32, C.c_float, VP, VP, VP]
+    lib.rs_pass_robust.restype = C.c_int
     lib.rs_denoise_var_device.argtypes = [VP, VP, VP, VP, C.c_uint32, C.c_uint32, C.c_uint32, C.c_float, C.c_float,
                                           C.c_float, C.c_int32, VP, VP, VP, VP]
     lib.rs_denoise_var_device.restype = C.c_int
@@ -289,7 +295,8 @@ EXPORTED_SYMBOLS = [
     "rs_scene_commit", "rs_scene_commit_devices", "rs_scene_get_info", "rs_scene_set_lanes",
     "rs_scene_set_frames_in_flight", "rs_scene_set_workspace", "rs_render", "rs_render_rows", "rs_render_device", "rs_render_device_passes", "rs_render_features", "rs_render_features_device", "rs_render_features_specular", "rs_render_features_specular_device", "rs_combine_pixels_device", "rs_noise_map_device", "rs_noise_map",
     "rs_denoise_device", "rs_denoise",
-    "rs_pass_moments_device", "rs_pass_moments", "rs_denoise_var_device", "rs_denoise_var",
+    "rs_pass_moments_device", "rs_pass_moments", "rs_pass_robust_device", "rs_pass_robust",
+    "rs_denoise_var_device", "rs_denoise_var",
     "rs_probe_world_hit", "rs_probe_samples", "rs_probe_shade",
 ]
 

@@ -787,6 +787,53 @@ def pass_moments_device(d_frame_ptrs: Sequence[int], width: int, height: int, d_
                                            d_var_ptr or None, stream_ptr or None), "rs_")
 
 
+def _robust_trim(trim, who: str) -> float:
+    """the C entry's trim of the Python layer's: None or "auto" = RS_ROBUST_TRIM_AUTO, else a finite float in [0, 0.5]"""
+    if trim is None or (isinstance(trim, str) and trim == "auto"):
+        return A.RS_ROBUST_TRIM_AUTO
+    if isinstance(trim, (str, bool)) or not isinstance(trim, (int, float, np.floating, np.integer)):
+        raise RaysnailError(A.RS_E_INVALID, f"{who}: trim is neither None / \"auto\" nor a number in [0, 0.5]")
+    t = float(trim)
+    if not (0.0 <= t <= 0.5):
+        raise RaysnailError(A.RS_E_INVALID, f"{who}: trim is neither None / \"auto\" nor a number in [0, 0.5]")
+    return t
+
+
+def pass_robust(frames: Sequence[np.ndarray], gamma: bool = True, trim: Optional[float] = None
+                ) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+    """rs_pass_robust on K (H, W, 4) float32 pass frames: pass_moments with the `trimmed` lowest and highest frames of
+    each pixel (ordered by r + g + b) cut from the mean and Winsorised in the variance. trim: the share cut at each
+    end, in [0, 0.5], or None for the Gini-driven trim. Returns (mean, var, trimmed): pass_moments' two frames and the
+    (H, W) uint8 count cut at each end."""
+    lib = A.load()
+    t = _robust_trim(trim, "pass_robust")
+    frames = [np.ascontiguousarray(f, dtype=np.float32) for f in frames]
+    if not frames:
+        raise RaysnailError(A.RS_E_INVALID, "pass_robust: n_frames outside 1 .. 64")
+    assert all(f.ndim == 3 and f.shape == frames[0].shape and f.shape[2] == 4 for f in frames)
+    H, W = frames[0].shape[:2]
+    ptrs = (C.c_void_p * len(frames))(*[C.c_void_p(f.ctypes.data) for f in frames])
+    mean, var = np.empty_like(frames[0]), np.empty_like(frames[0])
+    trimmed = np.empty((H, W), np.uint8)
+    _check(lib, lib.rs_pass_robust(ptrs, len(frames), W, H, int(bool(gamma)), t, mean.ctypes.data, var.ctypes.data,
+                                   trimmed.ctypes.data), "rs_")
+    return mean, var, trimmed
+
+
+def pass_robust_device(d_frame_ptrs: Sequence[int], width: int, height: int, d_mean_ptr: int, d_var_ptr: int,
+                       d_trimmed_ptr: int = 0, gamma: bool = True, trim: Optional[float] = None,
+                       stream_ptr: int = 0) -> None:
+    """rs_pass_robust_device on device frames: one launch enqueued on the stream, no synchronisation, no allocation.
+    d_mean_ptr or d_var_ptr may be 0 (not both), d_trimmed_ptr (W H bytes) may be 0; d_mean_ptr may be one of the
+    frames. trim as pass_robust's."""
+    lib = A.load()
+    t = _robust_trim(trim, "pass_robust")
+    n = len(d_frame_ptrs)
+    ptrs = (C.c_void_p * max(1, n))(*[C.c_void_p(p or None) for p in d_frame_ptrs])
+    _check(lib, lib.rs_pass_robust_device(ptrs, n, width, height, int(bool(gamma)), t, d_mean_ptr or None,
+                                          d_var_ptr or None, d_trimmed_ptr or None, stream_ptr or None), "rs_")
+
+
 @dataclass
 class DenoiseVarSettings:
     """rs_denoise_var's knobs; the defaults are the header's RS_DENOISE_VAR_* and RS_DENOISE_SIGMA_*."""
@@ -1078,14 +1125,17 @@ class TakePhotoSettings:
         return denoise(beauty, albedo, normal, settings, self._gamma), beauty
 
     def shot_denoised_passes(self, world: World, passes: int, pixel_map: Optional[PixelController] = None,
-                             settings: Optional[DenoiseVarSettings] = None, guide_specular: int = 0
-                             ) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+                             settings: Optional[DenoiseVarSettings] = None, guide_specular: int = 0,
+                             robust=None) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
         """`passes` (>= 2) progressive passes of the photo -- pass indices pass_index .. pass_index + passes - 1,
         `samples` each, every frame what shot gives for that pass -- and the first pass's feature frames (the same
         seed, rows and mask; shot_features' max_specular = guide_specular); then pass_moments and denoise_var with the
-        photo's gamma: returns (denoised, mean, var), (H, W, 4) float32 each. last_stats is the last pass's. No reference counterpart."""
+        photo's gamma: returns (denoised, mean, var), (H, W, 4) float32 each. last_stats is the last pass's. No reference counterpart.
+        robust: None = pass_moments (the default); "auto" or a trim in [0, 0.5] = pass_robust in its place."""
         if passes < 2:
             raise RaysnailError(A.RS_E_INVALID, "shot_denoised_passes: fewer than 2 passes")
+        if robust is not None:
+            _robust_trim(robust, "shot_denoised_passes")  # refused before anything renders
         first = self._pass
         frames = []
         try:
@@ -1097,7 +1147,10 @@ class TakePhotoSettings:
         stats = self.last_stats
         albedo, normal = self.shot_features(world, pixel_map, guide_specular)
         self.last_stats = stats
-        mean, var = pass_moments(frames, self._gamma)
+        if robust is None:
+            mean, var = pass_moments(frames, self._gamma)
+        else:
+            mean, var, _ = pass_robust(frames, self._gamma, None if robust == "auto" else robust)
         return denoise_var(mean, var, albedo, normal, settings, self._gamma), mean, var
 
     def shot_adaptive(self, world: World, settings: Optional[AdaptiveSettings] = None,

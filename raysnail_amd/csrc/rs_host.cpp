@@ -3367,6 +3367,62 @@ int rs_pass_moments(const float* const* frames, uint32_t n_frames, uint32_t widt
     });
 }
 
+// rs_pass_robust[_device]'s argument checks, before anything touches the device
+static void validate_pass_robust(const float* const* frames, uint32_t n_frames, uint32_t width, uint32_t height,
+                                 int32_t gamma, float trim, const float* mean, const float* var) {
+    if (n_frames < 1 || n_frames > 64) throw Error(RS_E_INVALID, "pass_robust: n_frames outside 1 .. 64");
+    if (gamma != 0 && gamma != 1) throw Error(RS_E_INVALID, "pass_robust: gamma is not 0 or 1");
+    if (trim != RS_ROBUST_TRIM_AUTO && !(trim >= 0.0f && trim <= 0.5f))  // (a NaN fails both)
+        throw Error(RS_E_INVALID, "pass_robust: trim is neither RS_ROBUST_TRIM_AUTO nor in [0, 0.5]");
+    const uint64_t n = (uint64_t)width * height;
+    if (n == 0) throw Error(RS_E_INVALID, "pass_robust: empty frame");
+    if (n > 0x7FFFFFFFull) throw Error(RS_E_INVALID, "pass_robust: frame too large");
+    if (!frames) throw Error(RS_E_INVALID, "pass_robust: null argument");
+    for (uint32_t k = 0; k < n_frames; ++k)
+        if (!frames[k]) throw Error(RS_E_INVALID, "pass_robust: null frame pointer");
+    if (!mean && !var) throw Error(RS_E_INVALID, "pass_robust: null argument (both outputs)");
+}
+
+int rs_pass_robust_device(const float* const* d_frames, uint32_t n_frames, uint32_t width, uint32_t height, int32_t gamma,
+                          float trim, float* d_mean, float* d_var, uint8_t* d_trimmed, void* stream) {
+    return run([&] {
+        validate_pass_robust(d_frames, n_frames, width, height, gamma, trim, d_mean, d_var);
+        HIP_OK(launch_pass_robust(d_frames, n_frames, width * height, gamma, trim, d_mean, d_var, d_trimmed,
+                                  (hipStream_t)stream));
+    });
+}
+
+int rs_pass_robust(const float* const* frames, uint32_t n_frames, uint32_t width, uint32_t height, int32_t gamma,
+                   float trim, float* mean, float* var, uint8_t* trimmed) {
+    return run([&] {
+        validate_pass_robust(frames, n_frames, width, height, gamma, trim, mean, var);
+        const size_t frame = (size_t)width * height * 4 * sizeof(float), fl = frame / sizeof(float);
+        // one allocation: the frames, then the mean, the variance and the trim counts
+        float* d = nullptr;
+        HIP_OK(hipMalloc((void**)&d, ((size_t)n_frames + 2) * frame + (size_t)width * height));
+        const float* d_frames[64];
+        hipError_t e = hipSuccess;
+        for (uint32_t k = 0; k < n_frames && e == hipSuccess; ++k) {
+            d_frames[k] = d + k * fl;
+            e = hipMemcpy(d + k * fl, frames[k], frame, hipMemcpyHostToDevice);
+        }
+        float* d_mean = mean ? d + (size_t)n_frames * fl : nullptr;
+        float* d_var = var ? d + ((size_t)n_frames + 1) * fl : nullptr;
+        uint8_t* d_trimmed = trimmed ? reinterpret_cast<uint8_t*>(d + ((size_t)n_frames + 2) * fl) : nullptr;
+        int rc = RS_OK;
+        if (e == hipSuccess)
+            rc = rs_pass_robust_device(d_frames, n_frames, width, height, gamma, trim, d_mean, d_var, d_trimmed, nullptr);
+        if (e == hipSuccess && rc == RS_OK) e = hipStreamSynchronize(nullptr);
+        if (e == hipSuccess && rc == RS_OK && mean) e = hipMemcpy(mean, d_mean, frame, hipMemcpyDeviceToHost);
+        if (e == hipSuccess && rc == RS_OK && var) e = hipMemcpy(var, d_var, frame, hipMemcpyDeviceToHost);
+        if (e == hipSuccess && rc == RS_OK && trimmed)
+            e = hipMemcpy(trimmed, d_trimmed, (size_t)width * height, hipMemcpyDeviceToHost);
+        (void)hipFree(d);
+        HIP_OK(e);
+        if (rc != RS_OK) throw Error(rc, g_last_error);
+    });
+}
+
 int rs_denoise_var_device(const float* d_beauty, const float* d_var, const float* d_albedo, const float* d_normal,
                           uint32_t width, uint32_t height, uint32_t levels, float k_color, float sigma_normal,
                           float sigma_depth, int32_t gamma, float* d_out, float* d_out_var, float* d_work, void* stream) {

@@ -254,6 +254,11 @@ hipError_t launch_pass_moments(const float* const* frames, uint32_t n_frames, ui
 hipError_t launch_denoise_var(const float* beauty, const float* var, const float* albedo, const float* normal,
                               uint32_t width, uint32_t height, uint32_t levels, float k_color, float inv_n, float inv_d,
                               int gamma, float* out, float* out_var, float* work, hipStream_t st);
+// The robust pass combine (rs_robust.hip; contract in raysnail_hip.h): one k_pass_robust launch, the frame pointers in
+// the argument block as launch_pass_moments'; trim in [0, 0.5] or negative for the Gini-driven trim; mean / var /
+// trimmed (n_pix bytes): any may be null.
+hipError_t launch_pass_robust(const float* const* frames, uint32_t n_frames, uint32_t n_pix, int gamma, float trim,
+                              float* mean, float* var, uint8_t* trimmed, hipStream_t st);
 // The adaptive pass loop's kernels (rs_adaptive.hip; contracts in raysnail_adaptive.h). launch_moments_update: one
 // k_moments_update launch, the frame pointers in the argument block as launch_pass_moments'. launch_moments_resolve:
 // mean / var, either may be null. launch_adaptive_mask: min_n, max_n <= 4096; tol2 = tolerance^2; counters: four zeroed

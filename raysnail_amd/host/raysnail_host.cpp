@@ -435,6 +435,26 @@ PassMoments pass_moments(const std::vector<std::vector<Pixel>>& frames, int W, i
     return m;
 }
 
+static bool robust_trim_valid(float trim) { return trim == ROBUST_AUTO || (trim >= 0.0f && trim <= 0.5f); }
+
+PassRobust pass_robust(const std::vector<std::vector<Pixel>>& frames, int W, int H, bool gamma, float trim) {
+    if (W < 0 || H < 0) throw Error(RS_E_INVALID, "pass_robust: negative size");
+    if (!robust_trim_valid(trim)) throw Error(RS_E_INVALID, "pass_robust: trim is neither ROBUST_AUTO nor in [0, 0.5]");
+    const size_t npx = (size_t)W * (size_t)H;
+    std::vector<const float*> ptrs;
+    for (const std::vector<Pixel>& f : frames) {
+        if (f.size() != npx) throw Error(RS_E_INVALID, "pass_robust: frame size mismatch");
+        ptrs.push_back(reinterpret_cast<const float*>(f.data()));
+    }
+    if (ptrs.size() > 64) throw Error(RS_E_INVALID, "pass_robust: n_frames outside 1 .. 64");
+    PassRobust m{std::vector<Pixel>(npx, Pixel{0.f, 0.f, 0.f, 0.f}), std::vector<Pixel>(npx, Pixel{0.f, 0.f, 0.f, 0.f}),
+                 std::vector<uint8_t>(npx, 0)};
+    check_rs(rs_pass_robust(ptrs.data(), (uint32_t)ptrs.size(), (uint32_t)W, (uint32_t)H, gamma ? 1 : 0, trim,
+                            reinterpret_cast<float*>(m.mean.data()), reinterpret_cast<float*>(m.var.data()),
+                            m.trimmed.data()));
+    return m;
+}
+
 void denoise_var(std::vector<Pixel>& pixels, const std::vector<Pixel>& var, const std::vector<Pixel>* albedo,
                  const std::vector<Pixel>* normal, int W, int H, const DenoiseVarSettings& settings, bool gamma,
                  std::vector<Pixel>* out_var) {
@@ -456,8 +476,10 @@ void denoise_var(std::vector<Pixel>& pixels, const std::vector<Pixel>& var, cons
 TakePhotoSettings::DenoisedPasses TakePhotoSettings::shot_denoised_passes(World& world, size_t passes,
                                                                           const PixelController* pixel_map,
                                                                           const DenoiseVarSettings& settings,
-                                                                          uint32_t guide_specular) {
+                                                                          uint32_t guide_specular, float robust) {
     if (passes < 2) throw Error(RS_E_INVALID, "shot_denoised_passes: fewer than 2 passes");
+    if (robust != ROBUST_OFF && !robust_trim_valid(robust))
+        throw Error(RS_E_INVALID, "shot_denoised_passes: robust is neither ROBUST_OFF, ROBUST_AUTO nor in [0, 0.5]");
     const uint32_t first = pass_;
     std::vector<std::vector<Pixel>> frames;
     try {
@@ -474,7 +496,14 @@ TakePhotoSettings::DenoisedPasses TakePhotoSettings::shot_denoised_passes(World&
     const Features f = shot_features(world, pixel_map, guide_specular);
     stats_ = last_pass_stats;
     const int W = (int)camera_.desc().width, H = (int)camera_.desc().height;
-    PassMoments m = pass_moments(frames, W, H, gamma_);
+    PassMoments m;
+    if (robust == ROBUST_OFF) {
+        m = pass_moments(frames, W, H, gamma_);
+    } else {
+        PassRobust r = pass_robust(frames, W, H, gamma_, robust);
+        m.mean = std::move(r.mean);
+        m.var = std::move(r.var);
+    }
     DenoisedPasses d;
     d.denoised = m.mean;
     denoise_var(d.denoised, m.var, &f.albedo, &f.normal, W, H, settings, gamma_);
