@@ -627,7 +627,7 @@ class DeviceScene:
         """rs_render_device_passes: passes st.pass + k into the device frames d_out_ptrs[k] (one sample stream on
         streaming scenes). stats as render_device."""
         n = len(d_out_ptrs)
-        ptrs = (C.c_void_p * max(1, n))(*[C.c_void_p(p) for p in d_out_ptrs])
+        ptrs = _ptr_array(d_out_ptrs)
         out = A.rs_render_stats() if stats else None
         _check(self.lib, self.lib.rs_render_device_passes(self.handle, C.byref(cam), C.byref(st), n, ptrs,
                                                           stream_ptr or None, C.byref(out) if stats else None), "rs_")
@@ -713,6 +713,24 @@ class DeviceScene:
         return mean, var, [passes[k] for k in range(n.value)]
 
 
+# ------------------------------------------------------------- frame operators' arguments ----
+def _frame(a, like: Optional[np.ndarray] = None) -> np.ndarray:
+    """a as a C-contiguous float32 (H, W, 4) frame (of like's shape where given)"""
+    a = np.ascontiguousarray(a, dtype=np.float32)
+    assert (a.ndim == 3 and a.shape[2] == 4) if like is None else a.shape == like.shape
+    return a
+
+
+def _data(a: Optional[np.ndarray]):
+    """the pointer argument of an optional array"""
+    return None if a is None else a.ctypes.data
+
+
+def _ptr_array(ptrs):
+    """the C array of the pointers (0: null); never of length zero"""
+    return (C.c_void_p * max(1, len(ptrs)))(*[C.c_void_p(p or None) for p in ptrs])
+
+
 # --------------------------------------------------------------------------- denoiser ----
 @dataclass
 class DenoiseSettings:
@@ -730,18 +748,11 @@ def denoise(beauty: np.ndarray, albedo: Optional[np.ndarray] = None, normal: Opt
     Returns a new frame."""
     lib = A.load()
     st = settings or DenoiseSettings()
-    beauty = np.ascontiguousarray(beauty, dtype=np.float32)
-    assert beauty.ndim == 3 and beauty.shape[2] == 4
+    beauty = _frame(beauty)
     H, W = beauty.shape[:2]
-    ptrs = []
-    for g in (albedo, normal):
-        if g is not None:
-            g = np.ascontiguousarray(g, dtype=np.float32)
-            assert g.shape == beauty.shape
-        ptrs.append(g)
+    albedo, normal = (None if g is None else _frame(g, beauty) for g in (albedo, normal))
     out = np.empty_like(beauty)
-    _check(lib, lib.rs_denoise(beauty.ctypes.data, None if ptrs[0] is None else ptrs[0].ctypes.data,
-                               None if ptrs[1] is None else ptrs[1].ctypes.data, W, H, st.levels, st.sigma_color,
+    _check(lib, lib.rs_denoise(beauty.ctypes.data, _data(albedo), _data(normal), W, H, st.levels, st.sigma_color,
                                st.sigma_normal, st.sigma_depth, int(bool(gamma)), out.ctypes.data), "rs_")
     return out
 
@@ -765,12 +776,12 @@ def pass_moments(frames: Sequence[np.ndarray], gamma: bool = True) -> Tuple[np.n
     of that mean in linear radiance over the n frames that contribute to the pixel. gamma: the frames carry the sqrt
     gamma."""
     lib = A.load()
-    frames = [np.ascontiguousarray(f, dtype=np.float32) for f in frames]
+    frames = [_frame(f) for f in frames]
     if not frames:
         raise RaysnailError(A.RS_E_INVALID, "pass_moments: n_frames outside 1 .. 64")
-    assert all(f.ndim == 3 and f.shape == frames[0].shape and f.shape[2] == 4 for f in frames)
+    assert all(f.shape == frames[0].shape for f in frames)
     H, W = frames[0].shape[:2]
-    ptrs = (C.c_void_p * len(frames))(*[C.c_void_p(f.ctypes.data) for f in frames])
+    ptrs = _ptr_array([f.ctypes.data for f in frames])
     mean, var = np.empty_like(frames[0]), np.empty_like(frames[0])
     _check(lib, lib.rs_pass_moments(ptrs, len(frames), W, H, int(bool(gamma)), mean.ctypes.data, var.ctypes.data), "rs_")
     return mean, var
@@ -782,7 +793,7 @@ def pass_moments_device(d_frame_ptrs: Sequence[int], width: int, height: int, d_
     Either output pointer may be 0 (not both); d_mean_ptr may be one of the frames."""
     lib = A.load()
     n = len(d_frame_ptrs)
-    ptrs = (C.c_void_p * max(1, n))(*[C.c_void_p(p or None) for p in d_frame_ptrs])
+    ptrs = _ptr_array(d_frame_ptrs)
     _check(lib, lib.rs_pass_moments_device(ptrs, n, width, height, int(bool(gamma)), d_mean_ptr or None,
                                            d_var_ptr or None, stream_ptr or None), "rs_")
 
@@ -807,12 +818,12 @@ def pass_robust(frames: Sequence[np.ndarray], gamma: bool = True, trim: Optional
     (H, W) uint8 count cut at each end."""
     lib = A.load()
     t = _robust_trim(trim, "pass_robust")
-    frames = [np.ascontiguousarray(f, dtype=np.float32) for f in frames]
+    frames = [_frame(f) for f in frames]
     if not frames:
         raise RaysnailError(A.RS_E_INVALID, "pass_robust: n_frames outside 1 .. 64")
-    assert all(f.ndim == 3 and f.shape == frames[0].shape and f.shape[2] == 4 for f in frames)
+    assert all(f.shape == frames[0].shape for f in frames)
     H, W = frames[0].shape[:2]
-    ptrs = (C.c_void_p * len(frames))(*[C.c_void_p(f.ctypes.data) for f in frames])
+    ptrs = _ptr_array([f.ctypes.data for f in frames])
     mean, var = np.empty_like(frames[0]), np.empty_like(frames[0])
     trimmed = np.empty((H, W), np.uint8)
     _check(lib, lib.rs_pass_robust(ptrs, len(frames), W, H, int(bool(gamma)), t, mean.ctypes.data, var.ctypes.data,
@@ -829,7 +840,7 @@ def pass_robust_device(d_frame_ptrs: Sequence[int], width: int, height: int, d_m
     lib = A.load()
     t = _robust_trim(trim, "pass_robust")
     n = len(d_frame_ptrs)
-    ptrs = (C.c_void_p * max(1, n))(*[C.c_void_p(p or None) for p in d_frame_ptrs])
+    ptrs = _ptr_array(d_frame_ptrs)
     _check(lib, lib.rs_pass_robust_device(ptrs, n, width, height, int(bool(gamma)), t, d_mean_ptr or None,
                                           d_var_ptr or None, d_trimmed_ptr or None, stream_ptr or None), "rs_")
 
@@ -851,24 +862,15 @@ def denoise_var(beauty: np.ndarray, var: np.ndarray, albedo: Optional[np.ndarray
     new frame, or with want_var the pair (frame, filtered variance frame)."""
     lib = A.load()
     st = settings or DenoiseVarSettings()
-    beauty = np.ascontiguousarray(beauty, dtype=np.float32)
-    assert beauty.ndim == 3 and beauty.shape[2] == 4
+    beauty = _frame(beauty)
     H, W = beauty.shape[:2]
-    var = np.ascontiguousarray(var, dtype=np.float32)
-    assert var.shape == beauty.shape
-    ptrs = []
-    for g in (albedo, normal):
-        if g is not None:
-            g = np.ascontiguousarray(g, dtype=np.float32)
-            assert g.shape == beauty.shape
-        ptrs.append(g)
+    var = _frame(var, beauty)
+    albedo, normal = (None if g is None else _frame(g, beauty) for g in (albedo, normal))
     out = np.empty_like(beauty)
     out_var = np.empty_like(beauty) if want_var else None
-    _check(lib, lib.rs_denoise_var(beauty.ctypes.data, var.ctypes.data,
-                                   None if ptrs[0] is None else ptrs[0].ctypes.data,
-                                   None if ptrs[1] is None else ptrs[1].ctypes.data, W, H, st.levels, st.k_color,
-                                   st.sigma_normal, st.sigma_depth, int(bool(gamma)), out.ctypes.data,
-                                   None if out_var is None else out_var.ctypes.data), "rs_")
+    _check(lib, lib.rs_denoise_var(beauty.ctypes.data, var.ctypes.data, _data(albedo), _data(normal), W, H, st.levels,
+                                   st.k_color, st.sigma_normal, st.sigma_depth, int(bool(gamma)), out.ctypes.data,
+                                   _data(out_var)), "rs_")
     return (out, out_var) if want_var else out
 
 
@@ -910,7 +912,7 @@ def moments_update_device(d_acc_ptr: int, d_m2_ptr: int, d_frame_ptrs: Sequence[
     1 .. 64 device frames, in order. One launch on the stream, no synchronisation, no allocation."""
     lib = A.load()
     n = len(d_frame_ptrs)
-    ptrs = (C.c_void_p * max(1, n))(*[C.c_void_p(p or None) for p in d_frame_ptrs])
+    ptrs = _ptr_array(d_frame_ptrs)
     _check(lib, lib.rs_moments_update_device(d_acc_ptr or None, d_m2_ptr or None, ptrs, n, width, height,
                                              int(gamma), stream_ptr or None), "rs_")
 

@@ -7,23 +7,15 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "rs_internal.h"
+#include "rs_frame_dev.h"
 
 namespace rs {
 namespace {
 
-__device__ __forceinline__ bool ad_finite(float v) { return (__float_as_uint(v) & 0x7F800000u) != 0x7F800000u; }
-__device__ __forceinline__ bool ad_finite3(const float4& v) { return ad_finite(v.x) && ad_finite(v.y) && ad_finite(v.z); }
-
 // ------------------------------------------------------------------------------------ Welford update ----
-constexpr int kAdMaxFrames = 64;
-struct AdFrames {
-    const float4* f[kAdMaxFrames];  // in the kernel's argument block: read with scalar loads, k is wave-uniform
-};
-
 // One thread per pixel: its state in registers over the frames, stored once, and only when a frame contributed.
 __global__ __launch_bounds__(kBlock) void k_moments_update(float4* __restrict__ acc, float4* __restrict__ m2,
-                                                           const AdFrames fr, const int n_frames, const uint32_t n_pix,
+                                                           const Frames fr, const int n_frames, const uint32_t n_pix,
                                                            const int gamma) {
     const uint32_t p = blockIdx.x * (uint32_t)kBlock + threadIdx.x;
     if (p >= n_pix) return;
@@ -32,8 +24,8 @@ __global__ __launch_bounds__(kBlock) void k_moments_update(float4* __restrict__ 
     bool any = false;
     for (int k = 0; k < n_frames; ++k) {
         float4 x = fr.f[k][p];
-        const bool take = x.w != 0.f && ad_finite3(x);
-        if (gamma) { x.x = x.x * x.x; x.y = x.y * x.y; x.z = x.z * x.z; }
+        const bool take = x.w != 0.f && finite3(x);
+        decode(x, gamma);
         const float n1 = a.w + 1.0f;
         const float dx = x.x - a.x, dy = x.y - a.y, dz = x.z - a.z;
         const float mx = a.x + dx / n1, my = a.y + dy / n1, mz = a.z + dz / n1;
@@ -58,18 +50,10 @@ __global__ __launch_bounds__(kBlock) void k_moments_resolve(const float4* __rest
     if (p >= n_pix) return;
     const float4 a = acc[p];
     const float n = a.w;
-    if (mean) {
-        const bool any = n >= 1.0f;
-        float ox = a.x, oy = a.y, oz = a.z;
-        if (gamma) { ox = sqrtf(ox); oy = sqrtf(oy); oz = sqrtf(oz); }
-        mean[p] = make_float4(any ? ox : 0.f, any ? oy : 0.f, any ? oz : 0.f, any ? 1.0f : 0.f);
-    }
+    if (mean) store_mean(mean, p, gamma, n >= 1.0f, a.x, a.y, a.z);
     if (var) {
         const float4 q = m2[p];
-        const bool two = n >= 2.0f;
-        const float den = n * (n - 1.0f);
-        const float vx = q.x / den, vy = q.y / den, vz = q.z / den;
-        var[p] = make_float4(two ? vx : 0.f, two ? vy : 0.f, two ? vz : 0.f, n);
+        var[p] = var_pixel(n >= 2.0f, q.x, q.y, q.z, n * (n - 1.0f), n);
     }
 }
 
@@ -115,7 +99,7 @@ __global__ __launch_bounds__(kBlock) void k_adaptive_mask(const AdMask A, const 
             const bool on_rows = gy >= A.row_begin && gy < A.row_end && (gy - A.row_begin) % A.row_step == 0;
             const bool based = on_rows && (A.base ? A.base[q] != 0 : true);
             const float n = a.w;
-            const bool fin = ad_finite3(a) && ad_finite3(m);
+            const bool fin = finite3(a) && finite3(m);
             const float t = (m.x + m.y) + m.z;
             const float v = t / (n * (n - 1.0f));
             const float L = (a.x + a.y) + a.z;
@@ -162,11 +146,9 @@ __global__ __launch_bounds__(kBlock) void k_adaptive_mask(const AdMask A, const 
 
 hipError_t launch_moments_update(float* acc, float* m2, const float* const* frames, uint32_t n_frames, uint32_t n_pix,
                                  int gamma, hipStream_t st) {
-    AdFrames fr;
-    for (uint32_t k = 0; k < (uint32_t)kAdMaxFrames; ++k)  // (the unused slots repeat frame 0: never read)
-        fr.f[k] = reinterpret_cast<const float4*>(frames[k < n_frames ? k : 0]);
     k_moments_update<<<dim3((n_pix + kBlock - 1) / kBlock), dim3(kBlock), 0, st>>>(
-        reinterpret_cast<float4*>(acc), reinterpret_cast<float4*>(m2), fr, (int)n_frames, n_pix, gamma);
+        reinterpret_cast<float4*>(acc), reinterpret_cast<float4*>(m2), frame_list(frames, n_frames), (int)n_frames, n_pix,
+        gamma);
     return hipGetLastError();
 }
 

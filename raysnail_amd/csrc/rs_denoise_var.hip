@@ -1,39 +1,19 @@
 // rs_denoise_var.hip — the pass moments (rs_pass_moments_device) and the variance-guided a-trous denoiser
 // (rs_denoise_var_device); the contracts, operation by operation, are in include/raysnail_hip.h. All f32, every
 // operation rounded once (the unit is built with -ffp-contract=off like the others), no transcendental. Needs nothing
-// of the scene: no rs_device.h. The helpers rs_denoise.hip has too (finite tests, modulation, the component-wise
-// select) are restated here: that unit's code stays as it is.
+// of the scene: no rs_device.h.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "rs_internal.h"
+#include "rs_frame_dev.h"
 
 namespace rs {
 namespace {
 
-__device__ __forceinline__ bool dv_finite(float v) { return (__float_as_uint(v) & 0x7F800000u) != 0x7F800000u; }
-__device__ __forceinline__ bool dv_finite3(const float4& v) { return dv_finite(v.x) && dv_finite(v.y) && dv_finite(v.z); }
-
-// m of rs_denoise's prepare step
-__device__ __forceinline__ float4 dv_modulation(const float4& alb) {
-    const float u = 1.0f - alb.w;  // the un-covered share counts as albedo 1
-    return make_float4(fmaxf(alb.x + u, 1e-3f), fmaxf(alb.y + u, 1e-3f), fmaxf(alb.z + u, 1e-3f), 0.f);
-}
-
-// (a ?: on two float4 objects selects between their addresses: both go to scratch)
-__device__ __forceinline__ float4 dv_select(const bool t, const float4 a, const float4 b) {
-    return make_float4(t ? a.x : b.x, t ? a.y : b.y, t ? a.z : b.z, t ? a.w : b.w);
-}
-
 // ------------------------------------------------------------------------------------ pass moments ----
-constexpr int kPmMaxFrames = 64;
-struct PmFrames {
-    const float4* f[kPmMaxFrames];  // in the kernel's argument block: read with scalar loads, k is wave-uniform
-};
-
 // One thread per pixel, two sweeps over the frames (the second finds its lines in L2 / Infinity Cache). Every load of
 // a thread comes before its stores, and it stores only its own pixel: mean may alias a frame (no __restrict__ here).
-__global__ __launch_bounds__(kBlock) void k_pass_moments(const PmFrames fr, const int n_frames, const uint32_t n_pix,
+__global__ __launch_bounds__(kBlock) void k_pass_moments(const Frames fr, const int n_frames, const uint32_t n_pix,
                                                          const int gamma, float4* mean, float4* var) {
     const uint32_t p = blockIdx.x * (uint32_t)kBlock + threadIdx.x;
     if (p >= n_pix) return;
@@ -41,8 +21,8 @@ __global__ __launch_bounds__(kBlock) void k_pass_moments(const PmFrames fr, cons
     int n = 0;
     for (int k = 0; k < n_frames; ++k) {
         float4 x = fr.f[k][p];
-        const bool take = x.w != 0.f && dv_finite3(x);
-        if (gamma) { x.x = x.x * x.x; x.y = x.y * x.y; x.z = x.z * x.z; }
+        const bool take = x.w != 0.f && finite3(x);
+        decode(x, gamma);
         sx = take ? sx + x.x : sx;
         sy = take ? sy + x.y : sy;
         sz = take ? sz + x.z : sz;
@@ -53,24 +33,15 @@ __global__ __launch_bounds__(kBlock) void k_pass_moments(const PmFrames fr, cons
     float qx = 0.f, qy = 0.f, qz = 0.f;
     for (int k = 0; k < n_frames; ++k) {
         float4 x = fr.f[k][p];
-        const bool take = x.w != 0.f && dv_finite3(x);
-        if (gamma) { x.x = x.x * x.x; x.y = x.y * x.y; x.z = x.z * x.z; }
+        const bool take = x.w != 0.f && finite3(x);
+        decode(x, gamma);
         const float dx = x.x - mx, dy = x.y - my, dz = x.z - mz;
         qx = take ? qx + dx * dx : qx;
         qy = take ? qy + dy * dy : qy;
         qz = take ? qz + dz * dz : qz;
     }
-    const bool any = n >= 1, two = n >= 2;
-    if (mean) {
-        float ox = mx, oy = my, oz = mz;
-        if (gamma) { ox = sqrtf(ox); oy = sqrtf(oy); oz = sqrtf(oz); }
-        mean[p] = make_float4(any ? ox : 0.f, any ? oy : 0.f, any ? oz : 0.f, any ? 1.0f : 0.f);
-    }
-    if (var) {
-        const float den = fn * (float)(n - 1);
-        const float vx = qx / den, vy = qy / den, vz = qz / den;
-        var[p] = make_float4(two ? vx : 0.f, two ? vy : 0.f, two ? vz : 0.f, fn);
-    }
+    if (mean) store_mean(mean, p, gamma, n >= 1, mx, my, mz);
+    if (var) var[p] = var_pixel(n >= 2, qx, qy, qz, fn * (float)(n - 1), fn);
 }
 
 // --------------------------------------------------------------------- variance-guided a-trous filter ----
@@ -86,23 +57,23 @@ __global__ __launch_bounds__(kBlock) void k_dv_prepare(const float4* beauty, con
     if (p >= n) return;
     const float4 b = beauty[p];
     const float4 V = var[p];
-    bool usable = b.w != 0.f && dv_finite3(b);
-    usable = usable && dv_finite3(V) && V.x >= 0.f && V.y >= 0.f && V.z >= 0.f;
+    bool usable = b.w != 0.f && finite3(b);
+    usable = usable && finite3(V) && V.x >= 0.f && V.y >= 0.f && V.z >= 0.f;
     float4 c = b, v = V;
-    if (gamma) { c.x = c.x * c.x; c.y = c.y * c.y; c.z = c.z * c.z; }
+    decode(c, gamma);
     if (albedo) {
         const float4 a = albedo[p];
-        usable = usable && dv_finite3(a) && dv_finite(a.w);
-        const float4 m = dv_modulation(a);
+        usable = usable && finite3(a) && finite(a.w);
+        const float4 m = modulation(a);
         c.x = c.x / m.x; c.y = c.y / m.y; c.z = c.z / m.z;
         const float mmx = m.x * m.x, mmy = m.y * m.y, mmz = m.z * m.z;
         v.x = v.x / mmx; v.y = v.y / mmy; v.z = v.z / mmz;
     }
     if (guide) {
         const float4 g = guide[p];
-        usable = usable && dv_finite3(g) && dv_finite(g.w);
+        usable = usable && finite3(g) && finite(g.w);
     }
-    usable = usable && dv_finite3(c) && dv_finite3(v);
+    usable = usable && finite3(c) && finite3(v);
     c.w = usable ? 1.0f : 0.0f;
     const float t = (v.x + v.y) + v.z;
     v.w = usable ? t : -1.0f;
@@ -132,9 +103,7 @@ __device__ __forceinline__ float dv_inv_variance(const float4* __restrict__ vin,
     float num = 0.f, den = 0.f;
 #pragma unroll
     for (int dy = -1; dy <= 1; ++dy) {
-        const int qy = y + dy;
-        const bool in_y = (unsigned)qy < (unsigned)H;
-        const int cy = min(max(qy, 0), H - 1);
+        const Tap qy = tap_at(y + dy, H);
 #pragma unroll
         for (int dx = -1; dx <= 1; ++dx) {
             const float gw = g[dx + 1] * g[dy + 1];
@@ -142,11 +111,9 @@ __device__ __forceinline__ float dv_inv_variance(const float4* __restrict__ vin,
                 num = num + gw * tp; den = den + gw;
                 continue;
             }
-            const int qx = x + dx;
-            const bool in_x = (unsigned)qx < (unsigned)W;
-            const int cx = min(max(qx, 0), W - 1);
-            const float t = vin[(uint32_t)cy * (uint32_t)W + (uint32_t)cx].w;
-            const bool take = in_y && in_x && !(t < 0.f);
+            const Tap qx = tap_at(x + dx, W);
+            const float t = vin[(uint32_t)qy.c * (uint32_t)W + (uint32_t)qx.c].w;
+            const bool take = qy.in && qx.in && !(t < 0.f);
             num = take ? num + gw * t : num;
             den = take ? den + gw : den;
         }
@@ -155,16 +122,12 @@ __device__ __forceinline__ float dv_inv_variance(const float4* __restrict__ vin,
     return 1.0f / (kc * vs + 1e-6f);  // RS_DENOISE_VAR_EPS
 }
 
-// One thread per pixel, every tap from global memory; block = a 64 x 4 tile, as rs_denoise's k_dn_atrous (a wave's
-// tap load is one contiguous 1 KiB run per plane).
-constexpr int kDvTileW = 64, kDvTileH = 4;
-static_assert(kDvTileW * kDvTileH == kBlock, "one thread per tile pixel");
-
+// One thread per pixel of a 64 x 4 tile (rs_frame_dev.h), as rs_denoise's k_dn_atrous.
 template <bool GUIDE, bool LAST>
 __global__ __launch_bounds__(kBlock) void k_dv_atrous(const DvLevel L, const uint32_t tiles_x) {
     const uint32_t ty = blockIdx.x / tiles_x, tx = blockIdx.x - ty * tiles_x;
-    const int x = (int)(tx * kDvTileW + (threadIdx.x & (kDvTileW - 1)));
-    const int y = (int)(ty * kDvTileH + (threadIdx.x / kDvTileW));
+    const int x = (int)(tx * kTileW + (threadIdx.x & (kTileW - 1)));
+    const int y = (int)(ty * kTileH + (threadIdx.x / kTileW));
     const int W = L.W, H = L.H, s = L.s;
     if (x >= W || y >= H) return;
     const uint32_t p = (uint32_t)y * (uint32_t)W + (uint32_t)x;
@@ -178,47 +141,31 @@ __global__ __launch_bounds__(kBlock) void k_dv_atrous(const DvLevel L, const uin
     const float iv = dv_inv_variance(vin, x, y, W, H, L.kc, vp.w);
     const float inv_n = L.inv_n, inv_d = L.inv_d;
 
-    const float k[5] = {0.0625f, 0.25f, 0.375f, 0.25f, 0.0625f};
     float sr = 0.f, sg = 0.f, sb = 0.f, sw = 0.f, vr = 0.f, vg = 0.f, vb = 0.f;
 #pragma unroll
     for (int dy = -2; dy <= 2; ++dy) {
-        const int qy = y + s * dy;
-        const bool in_y = (unsigned)qy < (unsigned)H;
-        const int cy = min(max(qy, 0), H - 1);
+        const Tap qy = tap_at(y + s * dy, H);
 #pragma unroll
         for (int dx = -2; dx <= 2; ++dx) {
-            const float h = k[dx + 2] * k[dy + 2];
+            const float h = b3_tap(dx + 2) * b3_tap(dy + 2);
             if (dx == 0 && dy == 0) {
                 const float hh = h * h;
                 sr = sr + h * cp.x; sg = sg + h * cp.y; sb = sb + h * cp.z; sw = sw + h;
                 vr = vr + hh * vp.x; vg = vg + hh * vp.y; vb = vb + hh * vp.z;
                 continue;
             }
-            const int qx = x + s * dx;
-            const bool in_x = (unsigned)qx < (unsigned)W;
-            const int cx = min(max(qx, 0), W - 1);
-            const uint32_t q = (uint32_t)cy * (uint32_t)W + (uint32_t)cx;
+            const Tap qx = tap_at(x + s * dx, W);
+            const uint32_t q = (uint32_t)qy.c * (uint32_t)W + (uint32_t)qx.c;
             const float4 cq = cin[q];
             const float4 vq = vin[q];
             const float dr = cq.x - cp.x, dg = cq.y - cp.y, db = cq.z - cp.z;
             const float dc2 = (dr * dr + dg * dg) + db * db;
             const float A = 1.0f + dc2 * iv;
             float w;
-            if (GUIDE) {
-                const float4 gq = gin[q];
-                const float nx = gq.x - gp.x, ny = gq.y - gp.y, nz = gq.z - gp.z;
-                const float dn2 = (nx * nx + ny * ny) + nz * nz;
-                const float dd = gq.w - gp.w;
-                const float M = fmaxf(fmaxf(fabsf(gp.w), fabsf(gq.w)), 1e-6f);
-                const float M2 = M * M;
-                const float B = 1.0f + dn2 * inv_n;
-                const float D = M2 + (dd * dd) * inv_d;
-                w = h * (M2 / ((A * B) * D));
-            } else {
-                w = h * (1.0f / A);
-            }
+            if (GUIDE) w = guide_weight(A, gp, gin[q], inv_n, inv_d, h);
+            else w = h * (1.0f / A);
             const float ww = w * w;
-            const bool take = in_y && in_x && cq.w != 0.f;
+            const bool take = qy.in && qx.in && cq.w != 0.f;
             sr = take ? sr + w * cq.x : sr;
             sg = take ? sg + w * cq.y : sg;
             sb = take ? sb + w * cq.z : sb;
@@ -234,13 +181,13 @@ __global__ __launch_bounds__(kBlock) void k_dv_atrous(const DvLevel L, const uin
 
     if (!LAST) {
         v.w = (v.x + v.y) + v.z;
-        L.cout[p] = dv_select(usable, c, cp);  // a pixel that is not usable is carried through untouched
-        L.vout[p] = dv_select(usable, v, vp);
+        L.cout[p] = select(usable, c, cp);  // a pixel that is not usable is carried through untouched
+        L.vout[p] = select(usable, v, vp);
         return;
     }
     const float4 b = L.beauty[p];
     if (L.albedo) {
-        const float4 m = dv_modulation(L.albedo[p]);
+        const float4 m = modulation(L.albedo[p]);
         c.x = c.x * m.x; c.y = c.y * m.y; c.z = c.z * m.z;
         const float mmx = m.x * m.x, mmy = m.y * m.y, mmz = m.z * m.z;
         v.x = v.x * mmx; v.y = v.y * mmy; v.z = v.z * mmz;
@@ -250,28 +197,18 @@ __global__ __launch_bounds__(kBlock) void k_dv_atrous(const DvLevel L, const uin
     if (L.vout) {  // (read before the colour store: out may be beauty, and out_var may be var)
         const float4 V = L.var[p];
         v.w = V.w;
-        L.vout[p] = dv_select(usable, v, V);
+        L.vout[p] = select(usable, v, V);
     }
-    L.cout[p] = dv_select(usable, c, b);
-}
-
-template <bool GUIDE, bool LAST>
-hipError_t dv_level(const DvLevel& L, hipStream_t st) {
-    const uint32_t tiles_x = ((uint32_t)L.W + kDvTileW - 1) / kDvTileW, tiles_y = ((uint32_t)L.H + kDvTileH - 1) / kDvTileH;
-    // W H <= 2^31 - 1 (checked by the caller), so tiles_x tiles_y < W H / 256 + W / 64 + H / 4 + 1 < 2^31
-    k_dv_atrous<GUIDE, LAST><<<dim3(tiles_x * tiles_y), dim3(kBlock), 0, st>>>(L, tiles_x);
-    return hipGetLastError();
+    L.cout[p] = select(usable, c, b);
 }
 
 }  // namespace
 
 hipError_t launch_pass_moments(const float* const* frames, uint32_t n_frames, uint32_t n_pix, int gamma, float* mean,
                                float* var, hipStream_t st) {
-    PmFrames fr;
-    for (uint32_t k = 0; k < (uint32_t)kPmMaxFrames; ++k)  // (the unused slots repeat frame 0: never read)
-        fr.f[k] = reinterpret_cast<const float4*>(frames[k < n_frames ? k : 0]);
     k_pass_moments<<<dim3((n_pix + kBlock - 1) / kBlock), dim3(kBlock), 0, st>>>(
-        fr, (int)n_frames, n_pix, gamma, reinterpret_cast<float4*>(mean), reinterpret_cast<float4*>(var));
+        frame_list(frames, n_frames), (int)n_frames, n_pix, gamma, reinterpret_cast<float4*>(mean),
+        reinterpret_cast<float4*>(var));
     return hipGetLastError();
 }
 
@@ -302,8 +239,8 @@ hipError_t launch_denoise_var(const float* beauty, const float* var, const float
         L.W = (int)width; L.H = (int)height; L.s = 1 << i;
         L.kc = k_color; L.inv_n = inv_n; L.inv_d = inv_d;
         L.gamma = gamma;
-        if (g4) e = last ? dv_level<true, true>(L, st) : dv_level<true, false>(L, st);
-        else e = last ? dv_level<false, true>(L, st) : dv_level<false, false>(L, st);
+        if (g4) e = launch_level(last ? k_dv_atrous<true, true> : k_dv_atrous<true, false>, L, st);
+        else e = launch_level(last ? k_dv_atrous<false, true> : k_dv_atrous<false, false>, L, st);
     }
     return e;
 }

@@ -28,6 +28,7 @@
 #include <vector>
 
 #include "../../include/raysnail_hip.h"
+#include "rs_host_util.h"
 #include "rs_internal.h"
 #include "rs_layout.h"
 
@@ -36,17 +37,6 @@ using namespace rs;
 namespace {
 
 thread_local std::string g_last_error;
-
-struct Error : std::runtime_error {
-    int code;
-    Error(int c, const std::string& m) : std::runtime_error(m), code(c) {}
-};
-
-#define HIP_OK(x)                                                                                          \
-    do {                                                                                                   \
-        hipError_t e_ = (x);                                                                               \
-        if (e_ != hipSuccess) throw Error(RS_E_HIP, std::string(#x " failed: ") + hipGetErrorString(e_)); \
-    } while (0)
 
 struct Box3 {
     double lo[3], hi[3];
@@ -1482,21 +1472,6 @@ bool carve_wf(Slot& L, uint64_t cap, uint32_t lanes) {
     return true;
 }
 
-struct DeviceGuard {
-    int prev = -1;
-    explicit DeviceGuard(int dev) {
-        HIP_OK(hipGetDevice(&prev));
-        if (prev != dev) HIP_OK(hipSetDevice(dev));
-    }
-    ~DeviceGuard() { if (prev >= 0) (void)hipSetDevice(prev); }
-};
-// Owners of what a render call creates for itself (move-only). An entry point drains the devices before these
-// go out of scope on an error: what it enqueued may still use them.
-template <class T, hipError_t (*Free)(T*)>
-struct HipFree { void operator()(T* p) const { (void)Free(p); } };
-using Event = std::unique_ptr<ihipEvent_t, HipFree<ihipEvent_t, hipEventDestroy>>;
-using DeviceMem = std::unique_ptr<void, HipFree<void, hipFree>>;
-using PinnedMem = std::unique_ptr<void, HipFree<void, hipHostFree>>;
 // record an untimed event, created when first recorded
 void record(Event& e, hipStream_t st) {
     if (!e) { hipEvent_t h; HIP_OK(hipEventCreateWithFlags(&h, hipEventDisableTiming)); e.reset(h); }
@@ -2848,8 +2823,7 @@ void render_frame_rows(rs_scene* s, const rs_camera_desc* cam, const rs_render_s
 
 }  // namespace
 
-namespace {
-int run(const std::function<void()>& f) {
+int rs::run(const std::function<void()>& f) {
     try {
         f();
         return RS_OK;
@@ -2864,6 +2838,7 @@ int run(const std::function<void()>& f) {
         return RS_E_INVALID;
     }
 }
+namespace {
 rs_scene* S(rs_scene* s) {
     if (!s) throw Error(RS_E_INVALID, "null scene");
     return s;
@@ -3202,357 +3177,7 @@ int rs_render_features_specular_device(rs_scene* s, const rs_camera_desc* cam, c
     });
 }
 
-int rs_combine_pixels_device(float* d_acc, const float* d_new, uint64_t n_pixels, float pass, void* stream) {
-    return run([&] {
-        if (!d_acc || !d_new) throw Error(RS_E_INVALID, "null argument");
-        HIP_OK(launch_combine(d_acc, d_new, n_pixels, pass, (hipStream_t)stream));
-    });
-}
-
-int rs_noise_map_device(const float* d_rgba, uint32_t width, uint32_t height, float threshold, uint8_t* d_redo,
-                        void* stream, rs_noise_stats* stats) {
-    return run([&] {
-        if (!d_rgba) throw Error(RS_E_INVALID, "null argument");
-        if ((uint64_t)width * height > 0x7FFFFFFFull) throw Error(RS_E_INVALID, "frame too large");
-        const hipStream_t st = (hipStream_t)stream;
-        // [0] min bits, [1] max bits (non-negative floats order like their bit patterns), [2..3] count
-        unsigned int* d = nullptr;
-        HIP_OK(hipMalloc((void**)&d, 4 * sizeof(unsigned int)));
-        unsigned int init[4];
-        float fmin0 = 3.0f, fmax0 = 1.0f;  // raysnail.rs:396-397
-        std::memcpy(&init[0], &fmin0, 4);
-        std::memcpy(&init[1], &fmax0, 4);
-        init[2] = init[3] = 0;
-        hipError_t e = hipMemcpyAsync(d, init, sizeof(init), hipMemcpyHostToDevice, st);
-        if (e == hipSuccess)
-            e = launch_noise(d_rgba, (int)width, (int)height, threshold, d_redo, d,
-                             reinterpret_cast<unsigned long long*>(d + 2), st);
-        unsigned int out[4] = {0, 0, 0, 0};
-        if (e == hipSuccess) e = hipMemcpyAsync(out, d, sizeof(out), hipMemcpyDeviceToHost, st);
-        if (e == hipSuccess) e = hipStreamSynchronize(st);
-        (void)hipFree(d);
-        HIP_OK(e);
-        if (stats) {
-            std::memcpy(&stats->min, &out[0], 4);
-            std::memcpy(&stats->max, &out[1], 4);
-            uint64_t c;
-            std::memcpy(&c, &out[2], 8);
-            stats->count = c;
-        }
-    });
-}
-
-int rs_noise_map(const float* rgba, uint32_t width, uint32_t height, float threshold, uint8_t* redo,
-                 rs_noise_stats* stats) {
-    return run([&] {
-        if (!rgba) throw Error(RS_E_INVALID, "null argument");
-        const size_t n = (size_t)width * height;
-        float* d_px = nullptr;
-        uint8_t* d_redo = nullptr;
-        HIP_OK(hipMalloc((void**)&d_px, n * 4 * sizeof(float) + 16));
-        hipError_t e = hipMalloc((void**)&d_redo, n + 16);
-        if (e == hipSuccess) e = hipMemcpy(d_px, rgba, n * 4 * sizeof(float), hipMemcpyHostToDevice);
-        int rc = RS_OK;
-        if (e == hipSuccess) rc = rs_noise_map_device(d_px, width, height, threshold, d_redo, nullptr, stats);
-        if (e == hipSuccess && rc == RS_OK && redo) e = hipMemcpy(redo, d_redo, n, hipMemcpyDeviceToHost);
-        (void)hipFree(d_px);
-        (void)hipFree(d_redo);
-        HIP_OK(e);
-        if (rc != RS_OK) throw Error(rc, g_last_error);
-    });
-}
-
-// rs_denoise[_device]'s argument checks (everything but the buffers), before anything touches the device
-static void validate_denoise(uint32_t width, uint32_t height, uint32_t levels, float sigma_color, float sigma_normal,
-                             float sigma_depth, int32_t gamma) {
-    if (levels < 1 || levels > 8) throw Error(RS_E_INVALID, "denoise: levels outside 1 .. 8");
-    for (float sg : {sigma_color, sigma_normal, sigma_depth})
-        if (!(sg >= 1e-4f && sg <= 1e4f)) throw Error(RS_E_INVALID, "denoise: sigma not finite or outside [1e-4, 1e4]");
-    if (gamma != 0 && gamma != 1) throw Error(RS_E_INVALID, "denoise: gamma is not 0 or 1");
-    const uint64_t n = (uint64_t)width * height;
-    if (n == 0) throw Error(RS_E_INVALID, "denoise: empty frame");
-    if (n > 0x7FFFFFFFull) throw Error(RS_E_INVALID, "denoise: frame too large");
-}
-
-int rs_denoise_device(const float* d_beauty, const float* d_albedo, const float* d_normal, uint32_t width, uint32_t height,
-                      uint32_t levels, float sigma_color, float sigma_normal, float sigma_depth, int32_t gamma,
-                      float* d_out, float* d_work, void* stream) {
-    return run([&] {
-        validate_denoise(width, height, levels, sigma_color, sigma_normal, sigma_depth, gamma);
-        if (!d_beauty || !d_out || !d_work) throw Error(RS_E_INVALID, "denoise: null argument");
-        // the contract's constants, in f32 (the colour sigma halves per level: an exact scaling)
-        float ic[8];
-        float sc = sigma_color;
-        for (uint32_t i = 0; i < levels; ++i, sc = sc * 0.5f) ic[i] = 1.0f / (sc * sc);
-        const float inv_n = 1.0f / (sigma_normal * sigma_normal), inv_d = 1.0f / (sigma_depth * sigma_depth);
-        HIP_OK(launch_denoise(d_beauty, d_albedo, d_normal, width, height, levels, ic, inv_n, inv_d, gamma, d_out, d_work,
-                              (hipStream_t)stream));
-    });
-}
-
-int rs_denoise(const float* beauty, const float* albedo, const float* normal, uint32_t width, uint32_t height,
-               uint32_t levels, float sigma_color, float sigma_normal, float sigma_depth, int32_t gamma, float* out) {
-    return run([&] {
-        validate_denoise(width, height, levels, sigma_color, sigma_normal, sigma_depth, gamma);
-        if (!beauty || !out) throw Error(RS_E_INVALID, "denoise: null argument");
-        const size_t frame = (size_t)width * height * 4 * sizeof(float);
-        // one allocation: beauty (the output, in place), albedo, normal, the two work planes
-        float* d = nullptr;
-        HIP_OK(hipMalloc((void**)&d, 5 * frame));
-        float* d_beauty = d;
-        float* d_albedo = albedo ? d + frame / sizeof(float) : nullptr;
-        float* d_normal = normal ? d + 2 * (frame / sizeof(float)) : nullptr;
-        float* d_work = d + 3 * (frame / sizeof(float));
-        hipError_t e = hipMemcpy(d_beauty, beauty, frame, hipMemcpyHostToDevice);
-        if (e == hipSuccess && albedo) e = hipMemcpy(d_albedo, albedo, frame, hipMemcpyHostToDevice);
-        if (e == hipSuccess && normal) e = hipMemcpy(d_normal, normal, frame, hipMemcpyHostToDevice);
-        int rc = RS_OK;
-        if (e == hipSuccess)
-            rc = rs_denoise_device(d_beauty, d_albedo, d_normal, width, height, levels, sigma_color, sigma_normal,
-                                   sigma_depth, gamma, d_beauty, d_work, nullptr);
-        if (e == hipSuccess && rc == RS_OK) e = hipStreamSynchronize(nullptr);
-        if (e == hipSuccess && rc == RS_OK) e = hipMemcpy(out, d_beauty, frame, hipMemcpyDeviceToHost);
-        (void)hipFree(d);
-        HIP_OK(e);
-        if (rc != RS_OK) throw Error(rc, g_last_error);
-    });
-}
-
-// rs_pass_moments[_device]'s argument checks, before anything touches the device
-static void validate_pass_moments(const float* const* frames, uint32_t n_frames, uint32_t width, uint32_t height,
-                                  int32_t gamma, const float* mean, const float* var) {
-    if (n_frames < 1 || n_frames > 64) throw Error(RS_E_INVALID, "pass_moments: n_frames outside 1 .. 64");
-    if (gamma != 0 && gamma != 1) throw Error(RS_E_INVALID, "pass_moments: gamma is not 0 or 1");
-    const uint64_t n = (uint64_t)width * height;
-    if (n == 0) throw Error(RS_E_INVALID, "pass_moments: empty frame");
-    if (n > 0x7FFFFFFFull) throw Error(RS_E_INVALID, "pass_moments: frame too large");
-    if (!frames) throw Error(RS_E_INVALID, "pass_moments: null argument");
-    for (uint32_t k = 0; k < n_frames; ++k)
-        if (!frames[k]) throw Error(RS_E_INVALID, "pass_moments: null frame pointer");
-    if (!mean && !var) throw Error(RS_E_INVALID, "pass_moments: null argument (both outputs)");
-}
-
-int rs_pass_moments_device(const float* const* d_frames, uint32_t n_frames, uint32_t width, uint32_t height, int32_t gamma,
-                           float* d_mean, float* d_var, void* stream) {
-    return run([&] {
-        validate_pass_moments(d_frames, n_frames, width, height, gamma, d_mean, d_var);
-        HIP_OK(launch_pass_moments(d_frames, n_frames, width * height, gamma, d_mean, d_var, (hipStream_t)stream));
-    });
-}
-
-int rs_pass_moments(const float* const* frames, uint32_t n_frames, uint32_t width, uint32_t height, int32_t gamma,
-                    float* mean, float* var) {
-    return run([&] {
-        validate_pass_moments(frames, n_frames, width, height, gamma, mean, var);
-        const size_t frame = (size_t)width * height * 4 * sizeof(float), fl = frame / sizeof(float);
-        // one allocation: the frames, then the mean and the variance
-        float* d = nullptr;
-        HIP_OK(hipMalloc((void**)&d, ((size_t)n_frames + 2) * frame));
-        const float* d_frames[64];
-        hipError_t e = hipSuccess;
-        for (uint32_t k = 0; k < n_frames && e == hipSuccess; ++k) {
-            d_frames[k] = d + k * fl;
-            e = hipMemcpy(d + k * fl, frames[k], frame, hipMemcpyHostToDevice);
-        }
-        float* d_mean = mean ? d + (size_t)n_frames * fl : nullptr;
-        float* d_var = var ? d + ((size_t)n_frames + 1) * fl : nullptr;
-        int rc = RS_OK;
-        if (e == hipSuccess) rc = rs_pass_moments_device(d_frames, n_frames, width, height, gamma, d_mean, d_var, nullptr);
-        if (e == hipSuccess && rc == RS_OK) e = hipStreamSynchronize(nullptr);
-        if (e == hipSuccess && rc == RS_OK && mean) e = hipMemcpy(mean, d_mean, frame, hipMemcpyDeviceToHost);
-        if (e == hipSuccess && rc == RS_OK && var) e = hipMemcpy(var, d_var, frame, hipMemcpyDeviceToHost);
-        (void)hipFree(d);
-        HIP_OK(e);
-        if (rc != RS_OK) throw Error(rc, g_last_error);
-    });
-}
-
-// rs_pass_robust[_device]'s argument checks, before anything touches the device
-static void validate_pass_robust(const float* const* frames, uint32_t n_frames, uint32_t width, uint32_t height,
-                                 int32_t gamma, float trim, const float* mean, const float* var) {
-    if (n_frames < 1 || n_frames > 64) throw Error(RS_E_INVALID, "pass_robust: n_frames outside 1 .. 64");
-    if (gamma != 0 && gamma != 1) throw Error(RS_E_INVALID, "pass_robust: gamma is not 0 or 1");
-    if (trim != RS_ROBUST_TRIM_AUTO && !(trim >= 0.0f && trim <= 0.5f))  // (a NaN fails both)
-        throw Error(RS_E_INVALID, "pass_robust: trim is neither RS_ROBUST_TRIM_AUTO nor in [0, 0.5]");
-    const uint64_t n = (uint64_t)width * height;
-    if (n == 0) throw Error(RS_E_INVALID, "pass_robust: empty frame");
-    if (n > 0x7FFFFFFFull) throw Error(RS_E_INVALID, "pass_robust: frame too large");
-    if (!frames) throw Error(RS_E_INVALID, "pass_robust: null argument");
-    for (uint32_t k = 0; k < n_frames; ++k)
-        if (!frames[k]) throw Error(RS_E_INVALID, "pass_robust: null frame pointer");
-    if (!mean && !var) throw Error(RS_E_INVALID, "pass_robust: null argument (both outputs)");
-}
-
-int rs_pass_robust_device(const float* const* d_frames, uint32_t n_frames, uint32_t width, uint32_t height, int32_t gamma,
-                          float trim, float* d_mean, float* d_var, uint8_t* d_trimmed, void* stream) {
-    return run([&] {
-        validate_pass_robust(d_frames, n_frames, width, height, gamma, trim, d_mean, d_var);
-        HIP_OK(launch_pass_robust(d_frames, n_frames, width * height, gamma, trim, d_mean, d_var, d_trimmed,
-                                  (hipStream_t)stream));
-    });
-}
-
-int rs_pass_robust(const float* const* frames, uint32_t n_frames, uint32_t width, uint32_t height, int32_t gamma,
-                   float trim, float* mean, float* var, uint8_t* trimmed) {
-    return run([&] {
-        validate_pass_robust(frames, n_frames, width, height, gamma, trim, mean, var);
-        const size_t frame = (size_t)width * height * 4 * sizeof(float), fl = frame / sizeof(float);
-        // one allocation: the frames, then the mean, the variance and the trim counts
-        float* d = nullptr;
-        HIP_OK(hipMalloc((void**)&d, ((size_t)n_frames + 2) * frame + (size_t)width * height));
-        const float* d_frames[64];
-        hipError_t e = hipSuccess;
-        for (uint32_t k = 0; k < n_frames && e == hipSuccess; ++k) {
-            d_frames[k] = d + k * fl;
-            e = hipMemcpy(d + k * fl, frames[k], frame, hipMemcpyHostToDevice);
-        }
-        float* d_mean = mean ? d + (size_t)n_frames * fl : nullptr;
-        float* d_var = var ? d + ((size_t)n_frames + 1) * fl : nullptr;
-        uint8_t* d_trimmed = trimmed ? reinterpret_cast<uint8_t*>(d + ((size_t)n_frames + 2) * fl) : nullptr;
-        int rc = RS_OK;
-        if (e == hipSuccess)
-            rc = rs_pass_robust_device(d_frames, n_frames, width, height, gamma, trim, d_mean, d_var, d_trimmed, nullptr);
-        if (e == hipSuccess && rc == RS_OK) e = hipStreamSynchronize(nullptr);
-        if (e == hipSuccess && rc == RS_OK && mean) e = hipMemcpy(mean, d_mean, frame, hipMemcpyDeviceToHost);
-        if (e == hipSuccess && rc == RS_OK && var) e = hipMemcpy(var, d_var, frame, hipMemcpyDeviceToHost);
-        if (e == hipSuccess && rc == RS_OK && trimmed)
-            e = hipMemcpy(trimmed, d_trimmed, (size_t)width * height, hipMemcpyDeviceToHost);
-        (void)hipFree(d);
-        HIP_OK(e);
-        if (rc != RS_OK) throw Error(rc, g_last_error);
-    });
-}
-
-int rs_denoise_var_device(const float* d_beauty, const float* d_var, const float* d_albedo, const float* d_normal,
-                          uint32_t width, uint32_t height, uint32_t levels, float k_color, float sigma_normal,
-                          float sigma_depth, int32_t gamma, float* d_out, float* d_out_var, float* d_work, void* stream) {
-    return run([&] {
-        validate_denoise(width, height, levels, k_color, sigma_normal, sigma_depth, gamma);
-        if (!d_beauty || !d_var || !d_out || !d_work) throw Error(RS_E_INVALID, "denoise: null argument");
-        const float inv_n = 1.0f / (sigma_normal * sigma_normal), inv_d = 1.0f / (sigma_depth * sigma_depth);
-        HIP_OK(launch_denoise_var(d_beauty, d_var, d_albedo, d_normal, width, height, levels, k_color, inv_n, inv_d, gamma,
-                                  d_out, d_out_var, d_work, (hipStream_t)stream));
-    });
-}
-
-int rs_denoise_var(const float* beauty, const float* var, const float* albedo, const float* normal, uint32_t width,
-                   uint32_t height, uint32_t levels, float k_color, float sigma_normal, float sigma_depth, int32_t gamma,
-                   float* out, float* out_var) {
-    return run([&] {
-        validate_denoise(width, height, levels, k_color, sigma_normal, sigma_depth, gamma);
-        if (!beauty || !var || !out) throw Error(RS_E_INVALID, "denoise: null argument");
-        const size_t frame = (size_t)width * height * 4 * sizeof(float), fl = frame / sizeof(float);
-        // one allocation: beauty and var (the outputs, in place), albedo, normal, the four work planes
-        float* d = nullptr;
-        HIP_OK(hipMalloc((void**)&d, 8 * frame));
-        float* d_beauty = d;
-        float* d_var = d + fl;
-        float* d_albedo = albedo ? d + 2 * fl : nullptr;
-        float* d_normal = normal ? d + 3 * fl : nullptr;
-        float* d_work = d + 4 * fl;
-        hipError_t e = hipMemcpy(d_beauty, beauty, frame, hipMemcpyHostToDevice);
-        if (e == hipSuccess) e = hipMemcpy(d_var, var, frame, hipMemcpyHostToDevice);
-        if (e == hipSuccess && albedo) e = hipMemcpy(d_albedo, albedo, frame, hipMemcpyHostToDevice);
-        if (e == hipSuccess && normal) e = hipMemcpy(d_normal, normal, frame, hipMemcpyHostToDevice);
-        int rc = RS_OK;
-        if (e == hipSuccess)
-            rc = rs_denoise_var_device(d_beauty, d_var, d_albedo, d_normal, width, height, levels, k_color, sigma_normal,
-                                       sigma_depth, gamma, d_beauty, out_var ? d_var : nullptr, d_work, nullptr);
-        if (e == hipSuccess && rc == RS_OK) e = hipStreamSynchronize(nullptr);
-        if (e == hipSuccess && rc == RS_OK) e = hipMemcpy(out, d_beauty, frame, hipMemcpyDeviceToHost);
-        if (e == hipSuccess && rc == RS_OK && out_var) e = hipMemcpy(out_var, d_var, frame, hipMemcpyDeviceToHost);
-        (void)hipFree(d);
-        HIP_OK(e);
-        if (rc != RS_OK) throw Error(rc, g_last_error);
-    });
-}
-
-// ---- adaptive sampling (rs_adaptive.hip) ----
-static void validate_frame_size(uint32_t width, uint32_t height, const char* what) {
-    const uint64_t n = (uint64_t)width * height;
-    if (n == 0) throw Error(RS_E_INVALID, std::string(what) + ": empty frame");
-    if (n > 0x7FFFFFFFull) throw Error(RS_E_INVALID, std::string(what) + ": frame too large");
-}
-
-static void validate_adaptive(uint32_t min_n, uint32_t max_n, float tolerance, float floor, uint32_t radius) {
-    if (min_n < 2) throw Error(RS_E_INVALID, "adaptive: min passes below 2");
-    if (max_n < min_n || max_n > 4096) throw Error(RS_E_INVALID, "adaptive: max passes below min passes or above 4096");
-    for (float v : {tolerance, floor})
-        if (!(v >= 1e-6f && v <= 1e4f)) throw Error(RS_E_INVALID, "adaptive: tolerance or floor not finite or outside [1e-6, 1e4]");
-    if (radius > 4) throw Error(RS_E_INVALID, "adaptive: radius above 4");
-}
-
-int rs_moments_update_device(float* d_acc, float* d_m2, const float* const* d_frames, uint32_t n_frames, uint32_t width,
-                             uint32_t height, int32_t gamma, void* stream) {
-    return run([&] {
-        if (n_frames < 1 || n_frames > 64) throw Error(RS_E_INVALID, "moments_update: n_frames outside 1 .. 64");
-        if (gamma != 0 && gamma != 1) throw Error(RS_E_INVALID, "moments_update: gamma is not 0 or 1");
-        validate_frame_size(width, height, "moments_update");
-        if (!d_acc || !d_m2 || !d_frames) throw Error(RS_E_INVALID, "moments_update: null argument");
-        for (uint32_t k = 0; k < n_frames; ++k)
-            if (!d_frames[k]) throw Error(RS_E_INVALID, "moments_update: null frame pointer");
-        HIP_OK(launch_moments_update(d_acc, d_m2, d_frames, n_frames, width * height, gamma, (hipStream_t)stream));
-    });
-}
-
-int rs_moments_resolve_device(const float* d_acc, const float* d_m2, uint32_t width, uint32_t height, int32_t gamma,
-                              float* d_mean, float* d_var, void* stream) {
-    return run([&] {
-        if (gamma != 0 && gamma != 1) throw Error(RS_E_INVALID, "moments_resolve: gamma is not 0 or 1");
-        validate_frame_size(width, height, "moments_resolve");
-        if (!d_acc || !d_m2) throw Error(RS_E_INVALID, "moments_resolve: null argument");
-        if (!d_mean && !d_var) throw Error(RS_E_INVALID, "moments_resolve: null argument (both outputs)");
-        HIP_OK(launch_moments_resolve(d_acc, d_m2, width * height, gamma, d_mean, d_var, (hipStream_t)stream));
-    });
-}
-
-// The mask launch with its statistics read back through `d_counters`: 16 bytes of device memory (one pixel of a frame)
-// that the stream may overwrite at this point. Synchronises the stream.
-static void adaptive_mask_stats(const float* d_acc, const float* d_m2, const uint8_t* d_base, uint32_t width, uint32_t height,
-                                uint32_t min_n, uint32_t max_n, float tol2, float floor, uint32_t radius, uint8_t* d_mask,
-                                unsigned int* d_counters, hipStream_t st, rs_adaptive_stats* stats, const RowSet& rows) {
-    HIP_OK(hipMemsetAsync(d_counters, 0, 4 * sizeof(unsigned int), st));
-    HIP_OK(launch_adaptive_mask(d_acc, d_m2, d_base, width, height, min_n, max_n, tol2, floor, radius, d_mask, d_counters, st,
-                                rows.begin, rows.end, rows.step));
-    unsigned int out[4] = {0, 0, 0, 0};
-    HIP_OK(hipMemcpyAsync(out, d_counters, sizeof(out), hipMemcpyDeviceToHost, st));
-    HIP_OK(hipMemsetAsync(d_counters, 0, 4 * sizeof(unsigned int), st));  // (left as an all-zero pixel: see the loop)
-    HIP_OK(hipStreamSynchronize(st));
-    stats->active = out[0];
-    stats->hot = out[1];
-    stats->nonfinite = out[2];
-    std::memcpy(&stats->max_err2, &out[3], 4);
-}
-
-int rs_adaptive_mask_device(const float* d_acc, const float* d_m2, const uint8_t* d_base, uint32_t width, uint32_t height,
-                            uint32_t min_n, uint32_t max_n, float tolerance, float floor, uint32_t radius, uint8_t* d_mask,
-                            void* stream, rs_adaptive_stats* stats) {
-    return run([&] {
-        validate_adaptive(min_n, max_n, tolerance, floor, radius);
-        validate_frame_size(width, height, "adaptive_mask");
-        if (!d_acc || !d_m2 || !d_mask) throw Error(RS_E_INVALID, "adaptive_mask: null argument");
-        const float tol2 = tolerance * tolerance;
-        const hipStream_t st = (hipStream_t)stream;
-        if (!stats) {
-            HIP_OK(launch_adaptive_mask(d_acc, d_m2, d_base, width, height, min_n, max_n, tol2, floor, radius, d_mask,
-                                        nullptr, st, 0, height, 1));
-            return;
-        }
-        unsigned int* d = nullptr;
-        HIP_OK(hipMalloc((void**)&d, 4 * sizeof(unsigned int)));
-        try {
-            RowSet all;
-            all.end = height;
-            adaptive_mask_stats(d_acc, d_m2, d_base, width, height, min_n, max_n, tol2, floor, radius, d_mask, d, st, stats, all);
-        } catch (...) {
-            (void)hipStreamSynchronize(st);
-            (void)hipFree(d);
-            throw;
-        }
-        (void)hipFree(d);
-    });
-}
-
+// ---- adaptive sampling (the operators it is made of: rs_frames.cpp) ----
 // rs_render_adaptive_device's loop: mask, stop or render, update. The mask's counters are the first 16 bytes of the
 // work frame (its first pixel: every frame has one), which holds nothing between a pass's update and the next pass's render.
 static void render_adaptive_device(rs_scene* s, const rs_camera_desc* cam, const rs_render_settings* st,
@@ -3582,7 +3207,8 @@ static void render_adaptive_device(rs_scene* s, const rs_camera_desc* cam, const
         {
             DeviceGuard g(dev0);
             adaptive_mask_stats(d_acc, d_m2, d_base, cam->width, cam->height, as->min_passes, as->max_passes, tol2, as->floor,
-                                as->radius, d_work_mask, reinterpret_cast<unsigned int*>(d_work_frame), stream, &ms, rows);
+                                as->radius, d_work_mask, reinterpret_cast<unsigned int*>(d_work_frame), stream, &ms, rows.begin, rows.end,
+                                rows.step);
         }
         if (ms.active == 0 || p == as->max_passes) break;
         rs_render_settings sp = *st;
@@ -3628,8 +3254,8 @@ int rs_render_adaptive(rs_scene* s, const rs_camera_desc* cam, const rs_render_s
         DeviceGuard g(s->reps[0]->device);
         const size_t npx = (size_t)cam->width * cam->height, frame = npx * 4 * sizeof(float), fl = npx * 4;
         // one allocation: acc, m2 (zeroed: the empty state), the work frame, one output frame, the two byte planes
-        float* d = nullptr;
-        HIP_OK(hipMalloc((void**)&d, 4 * frame + 2 * npx));
+        const DeviceMem mem = device_alloc(4 * frame + 2 * npx);
+        float* const d = static_cast<float*>(mem.get());
         float *d_acc = d, *d_m2 = d + fl, *d_work = d + 2 * fl, *d_out = d + 3 * fl;
         uint8_t* d_wmask = reinterpret_cast<uint8_t*>(d + 4 * fl);
         uint8_t* d_base = base_mask ? d_wmask + npx : nullptr;
@@ -3646,11 +3272,9 @@ int rs_render_adaptive(rs_scene* s, const rs_camera_desc* cam, const rs_render_s
                 HIP_OK(hipMemcpy(var, d_out, frame, hipMemcpyDeviceToHost));
             }
         } catch (...) {
-            (void)hipDeviceSynchronize();
-            (void)hipFree(d);
+            (void)hipDeviceSynchronize();  // drain what was enqueued before the buffers go away
             throw;
         }
-        (void)hipFree(d);
     });
 }
 

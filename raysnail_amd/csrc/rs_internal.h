@@ -19,6 +19,7 @@ constexpr int kStackMin = 16;
 constexpr uint32_t kLeafBatch = 8;
 constexpr uint32_t kMaxLanes = 4;   // chunk lanes of the bounce-synchronous wavefront (flat / rich scenes)
 constexpr uint32_t kMaxSlots = 4;   // frames in flight per replica (rs_scene_set_frames_in_flight)
+constexpr int kMaxFrames = 64;      // frames of one pass-operator call (their pointers ride in the kernel's argument block)
 
 // Scene modes (a template parameter of every path kernel): kSmSpheres -- world and lights are
 // spheres only (prim-indexed sphere copy, material-sorted wavefront); kSmFlat -- spheres, rects and

@@ -1,7 +1,6 @@
 // rs_robust.hip — the rank-trimmed mean of K pass frames and its Winsorised variance (rs_pass_robust_device); the
 // contract, operation by operation, is in include/raysnail_hip.h. All f32, every operation rounded once (the unit is
-// built with -ffp-contract=off like the others), no transcendental. Scene-free: no rs_device.h. The finite tests and
-// the component-wise select that rs_denoise_var.hip has too are restated here: that unit's code stays as it is.
+// built with -ffp-contract=off like the others), no transcendental. Scene-free: no rs_device.h.
 //
 // The frame count is a run-time value, so a per-thread array of keys would be indexed by a run-time k and go to
 // scratch. The keys live in LDS instead, one column per thread ([k][thread]: a wave's 64 lanes read 64 consecutive
@@ -13,26 +12,17 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "rs_internal.h"
+#include "rs_frame_dev.h"
 
 namespace rs {
 namespace {
 
 constexpr int kRbBlock = 128;  // 2 waves; 64 frames: 40 KB of LDS per block
-constexpr int kRbMaxFrames = 64;
-struct RbFrames {
-    const float4* f[kRbMaxFrames];  // in the kernel's argument block: read with scalar loads, k is wave-uniform
-};
 
-__device__ __forceinline__ bool rb_finite(float v) { return (__float_as_uint(v) & 0x7F800000u) != 0x7F800000u; }
-__device__ __forceinline__ bool rb_finite3(const float4& v) { return rb_finite(v.x) && rb_finite(v.y) && rb_finite(v.z); }
-// (a ?: on two float4 objects selects between their addresses: both go to scratch)
-__device__ __forceinline__ float4 rb_select(const bool t, const float4 a, const float4 b) {
-    return make_float4(t ? a.x : b.x, t ? a.y : b.y, t ? a.z : b.z, t ? a.w : b.w);
-}
 // frame k's x of the contract (the alpha is left as loaded)
-__device__ __forceinline__ float4 rb_value(const RbFrames& fr, const int k, const uint32_t p, const int gamma) {
+__device__ __forceinline__ float4 rb_value(const Frames& fr, const int k, const uint32_t p, const int gamma) {
     float4 x = fr.f[k][p];
+    // (not decode(), here and in the key loop: it reorders this kernel's registers)
     if (gamma) { x.x = x.x * x.x; x.y = x.y * x.y; x.z = x.z * x.z; }
     return x;
 }
@@ -42,7 +32,7 @@ __device__ __forceinline__ int rb_rank(const uint32_t* ranks, const int k) {
 
 // One thread per pixel. Every load of a thread comes before its stores, and it stores only its own pixel: mean may
 // alias a frame (no __restrict__ here).
-__global__ __launch_bounds__(kRbBlock) void k_pass_robust(const RbFrames fr, const int n_frames, const uint32_t n_pix,
+__global__ __launch_bounds__(kRbBlock) void k_pass_robust(const Frames fr, const int n_frames, const uint32_t n_pix,
                                                           const int gamma, const float trim, float4* mean, float4* var,
                                                           uint8_t* trimmed) {
     extern __shared__ float rb_lds[];
@@ -60,7 +50,7 @@ __global__ __launch_bounds__(kRbBlock) void k_pass_robust(const RbFrames fr, con
         float4 x = f;
         if (gamma) { x.x = x.x * x.x; x.y = x.y * x.y; x.z = x.z * x.z; }
         const float s = (x.x + x.y) + x.z;
-        const bool take = f.w != 0.f && rb_finite3(f) && rb_finite(s);
+        const bool take = f.w != 0.f && finite3(f) && finite(s);
         keys[k * kRbBlock] = take ? s : inf;
         n += take ? 1 : 0;
     }
@@ -92,7 +82,7 @@ __global__ __launch_bounds__(kRbBlock) void k_pass_robust(const RbFrames fr, con
             ranks[(kk >> 2) * kRbBlock] = (uint32_t)r0 | ((uint32_t)r1 << 8) | ((uint32_t)r2 << 16) | ((uint32_t)r3 << 24);
             if (automatic) {
                 const int nm1 = n - 1;
-                const bool c0 = rb_finite(a0), c1 = rb_finite(a1), c2 = rb_finite(a2), c3 = rb_finite(a3);
+                const bool c0 = finite(a0), c1 = finite(a1), c2 = finite(a2), c3 = finite(a3);
                 const float g0 = (float)(2 * r0 - nm1) * a0, g1 = (float)(2 * r1 - nm1) * a1;
                 const float g2 = (float)(2 * r2 - nm1) * a2, g3 = (float)(2 * r3 - nm1) * a3;
                 ss = c0 ? ss + a0 : ss; ng = c0 ? ng + g0 : ng;
@@ -123,14 +113,14 @@ __global__ __launch_bounds__(kRbBlock) void k_pass_robust(const RbFrames fr, con
     float4 xlo = make_float4(0.f, 0.f, 0.f, 0.f), xhi = xlo;
     for (int k = 0; k < n_frames; ++k) {
         const float4 x = rb_value(fr, k, p, gamma);
-        const bool c = rb_finite(keys[k * kRbBlock]);
+        const bool c = finite(keys[k * kRbBlock]);
         const int r = rb_rank(ranks, k);
         const bool kept = c && r >= t && r <= top;
         sx = kept ? sx + x.x : sx;
         sy = kept ? sy + x.y : sy;
         sz = kept ? sz + x.z : sz;
-        xlo = rb_select(c && r == t, x, xlo);
-        xhi = rb_select(c && r == top, x, xhi);
+        xlo = select(c && r == t, x, xlo);
+        xhi = select(c && r == top, x, xhi);
     }
     const float fh = (float)h;
     const float mx = sx / fh, my = sy / fh, mz = sz / fh;  // (n = 0: 0 / 0, dropped below)
@@ -141,9 +131,9 @@ __global__ __launch_bounds__(kRbBlock) void k_pass_robust(const RbFrames fr, con
         wx = 0.f; wy = 0.f; wz = 0.f;
         for (int k = 0; k < n_frames; ++k) {
             const float4 x = rb_value(fr, k, p, gamma);
-            const bool c = rb_finite(keys[k * kRbBlock]);
+            const bool c = finite(keys[k * kRbBlock]);
             const int r = rb_rank(ranks, k);
-            const float4 w = rb_select(r < t, xlo, rb_select(r > top, xhi, x));
+            const float4 w = select(r < t, xlo, select(r > top, xhi, x));
             wx = c ? wx + w.x : wx;
             wy = c ? wy + w.y : wy;
             wz = c ? wz + w.z : wz;
@@ -153,26 +143,22 @@ __global__ __launch_bounds__(kRbBlock) void k_pass_robust(const RbFrames fr, con
     float qx = 0.f, qy = 0.f, qz = 0.f;
     for (int k = 0; k < n_frames; ++k) {
         const float4 x = rb_value(fr, k, p, gamma);
-        const bool c = rb_finite(keys[k * kRbBlock]);
+        const bool c = finite(keys[k * kRbBlock]);
         const int r = rb_rank(ranks, k);
-        const float4 w = rb_select(r < t, xlo, rb_select(r > top, xhi, x));
+        const float4 w = select(r < t, xlo, select(r > top, xhi, x));
         const float dx = w.x - mwx, dy = w.y - mwy, dz = w.z - mwz;
         qx = c ? qx + dx * dx : qx;
         qy = c ? qy + dy * dy : qy;
         qz = c ? qz + dz * dz : qz;
     }
 
-    const bool any = n >= 1, two = n >= 2;
-    if (mean) {
+    if (mean) {  // (not store_mean(): it reorders this kernel's registers)
+        const bool any = n >= 1;
         float ox = mx, oy = my, oz = mz;
         if (gamma) { ox = sqrtf(ox); oy = sqrtf(oy); oz = sqrtf(oz); }
         mean[p] = make_float4(any ? ox : 0.f, any ? oy : 0.f, any ? oz : 0.f, any ? 1.0f : 0.f);
     }
-    if (var) {
-        const float den = fh * (float)(h - 1);
-        const float vx = qx / den, vy = qy / den, vz = qz / den;
-        var[p] = make_float4(two ? vx : 0.f, two ? vy : 0.f, two ? vz : 0.f, fn);
-    }
+    if (var) var[p] = var_pixel(n >= 2, qx, qy, qz, fh * (float)(h - 1), fn);
     if (trimmed) trimmed[p] = (uint8_t)t;
 }
 
@@ -180,13 +166,10 @@ __global__ __launch_bounds__(kRbBlock) void k_pass_robust(const RbFrames fr, con
 
 hipError_t launch_pass_robust(const float* const* frames, uint32_t n_frames, uint32_t n_pix, int gamma, float trim,
                               float* mean, float* var, uint8_t* trimmed, hipStream_t st) {
-    RbFrames fr;
-    for (uint32_t k = 0; k < (uint32_t)kRbMaxFrames; ++k)  // (the unused slots repeat frame 0: never read)
-        fr.f[k] = reinterpret_cast<const float4*>(frames[k < n_frames ? k : 0]);
     const uint32_t n4 = (n_frames + 3u) & ~3u;
     const size_t lds = (size_t)n4 * kRbBlock * 5;  // 4 bytes of key and 1 of rank per frame and thread: at most 40 KB
     k_pass_robust<<<dim3((n_pix + kRbBlock - 1) / kRbBlock), dim3(kRbBlock), lds, st>>>(
-        fr, (int)n_frames, n_pix, gamma, trim, reinterpret_cast<float4*>(mean), reinterpret_cast<float4*>(var), trimmed);
+        frame_list(frames, n_frames), (int)n_frames, n_pix, gamma, trim, reinterpret_cast<float4*>(mean), reinterpret_cast<float4*>(var), trimmed);
     return hipGetLastError();
 }
 

@@ -139,6 +139,12 @@ def test_host_entry_equals_device_entry(gpu, frames):
         for a, n, gamma in ((albedo, normal, 1), (None, normal, 0), (None, None, 1)):
             host = api.denoise(beauty, a, n, st, bool(gamma))
             assert np.array_equal(host.view(np.uint32), run_device(gpu, beauty, a, n, st, gamma).view(np.uint32))
+    # every guide combination of the host entry's staging, on a 67 x 5 frame: no multiple of the 64 x 4 tile or of the
+    # block, two tiles each way
+    beauty, albedo, normal = D.synthetic(67, 5, 12)
+    for a, n, gamma in ((None, None, 0), (albedo, None, 1), (None, normal, 1), (albedo, normal, 0)):
+        host = api.denoise(beauty, a, n, st, bool(gamma))
+        assert np.array_equal(host.view(np.uint32), run_device(gpu, beauty, a, n, st, gamma).view(np.uint32))
 
 
 def test_rendered_frame(gpu):

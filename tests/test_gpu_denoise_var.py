@@ -3,11 +3,14 @@ restatements of the header's contracts (tests/denoise_var_ref.py): denoise_ref's
 (smaller than any tile and than the level-4 reach) and 149 x 67 (several tiles in each direction with a remainder) plus
 a seeded variance frame with exact zeros, a block four orders of magnitude above the rest and coverage-weighted
 regions; and one rendered chain."""
+import ctypes as C
+
 import numpy as np
 import pytest
 
 import denoise_ref as D
 import denoise_var_ref as V
+from raysnail_amd import _abi as A
 from raysnail_amd import api, scenes
 
 pytestmark = pytest.mark.gpu
@@ -132,6 +135,18 @@ def test_moments_one_output_at_a_time_aliasing_and_side_stream(gpu, pass_frames)
         assert_same(var, exp_var)
 
 
+def host_moments(frames, gamma, want):
+    """rs_pass_moments with the wanted outputs only (api.pass_moments always asks for both): (mean, var), None where
+    not asked for"""
+    lib = A.load()
+    h, w = frames[0].shape[:2]
+    ptrs = (C.c_void_p * len(frames))(*[f.ctypes.data for f in frames])
+    outs = [np.full((h, w, 4), SENTINEL, np.float32) if on else None for on in want]
+    rc = lib.rs_pass_moments(ptrs, len(frames), w, h, gamma, *[None if o is None else o.ctypes.data for o in outs])
+    assert rc == 0, lib.rs_last_error()
+    return outs
+
+
 def test_moments_host_entry_equals_device_entry(gpu, pass_frames):
     for size in SIZES:
         for k, gamma in ((3, 1), (64, 0)):
@@ -139,6 +154,14 @@ def test_moments_host_entry_equals_device_entry(gpu, pass_frames):
             mean, var = api.pass_moments(frames, bool(gamma))
             dmean, dvar = run_moments(gpu, frames, gamma)
             assert np.array_equal(_bits(mean), _bits(dmean)) and np.array_equal(_bits(var), _bits(dvar))
+    # each output alone and both, on the 67 x 5 corner of the frames (no multiple of the block, the NaN and inf pixels
+    # inside), K = 3 and 5
+    small = [np.ascontiguousarray(f[:5, :67]) for f in pass_frames[SIZES[1]][:5]]
+    for k, gamma in ((3, 1), (5, 0)):
+        for want in ((True, True), (True, False), (False, True)):
+            host, dev = host_moments(small[:k], gamma, want), run_moments(gpu, small[:k], gamma, want)
+            for on, a, b in zip(want, host, dev):
+                assert (a is None and b is None) if not on else np.array_equal(_bits(a), _bits(b)), (k, want)
 
 
 # ---------------------------------------------------------------------------------- denoiser ----
@@ -271,6 +294,16 @@ def test_host_entry_equals_device_entry(gpu, frames):
             dev, dev_var = run_device(gpu, beauty, var, a, n, st, gamma)
             assert np.array_equal(_bits(host), _bits(dev)) and np.array_equal(_bits(host_var), _bits(dev_var))
             assert np.array_equal(_bits(api.denoise_var(beauty, var, a, n, st, bool(gamma))), _bits(dev))
+    # every guide combination with and without out_var, on a 67 x 5 frame: no multiple of the 64 x 4 tile or of the
+    # block, two tiles each way
+    beauty, albedo, normal = D.synthetic(67, 5, 12)
+    var = V.synthetic_variance(67, 5, 22, albedo)
+    for a, n, gamma in ((None, None, 0), (albedo, None, 1), (None, normal, 1), (albedo, normal, 0)):
+        host, host_var = api.denoise_var(beauty, var, a, n, st, bool(gamma), want_var=True)
+        dev, dev_var = run_device(gpu, beauty, var, a, n, st, gamma)
+        assert np.array_equal(_bits(host), _bits(dev)) and np.array_equal(_bits(host_var), _bits(dev_var))
+        dev, none = run_device(gpu, beauty, var, a, n, st, gamma, want_var=False)
+        assert none is None and np.array_equal(_bits(api.denoise_var(beauty, var, a, n, st, bool(gamma))), _bits(dev))
 
 
 # -------------------------------------------------------------------------------- end to end ----

@@ -3,11 +3,14 @@ contract (tests/robust_ref.py): test_gpu_denoise_var's seeded pass frames at 37 
 of a row) and 149 x 67 (many blocks with a remainder) with a band of equal frames, a band of exact key ties between
 different colours, fireflies planted in one and in two frames and a value whose square overflows added; and one
 rendered chain."""
+import ctypes as C
+
 import numpy as np
 import pytest
 
 import denoise_var_ref as V
 import robust_ref as R
+from raysnail_amd import _abi as A
 from raysnail_amd import api
 
 pytestmark = pytest.mark.gpu
@@ -192,6 +195,20 @@ def test_each_output_null_aliasing_and_side_stream(gpu, pass_frames):
             check(torch, frames, 1, trim, stream=torch.cuda.Stream())
 
 
+def host_robust(frames, gamma, trim, want):
+    """rs_pass_robust with the wanted outputs only (api.pass_robust always asks for all three): (mean, var, trimmed),
+    None where not asked for"""
+    lib = A.load()
+    h, w = frames[0].shape[:2]
+    ptrs = (C.c_void_p * len(frames))(*[f.ctypes.data for f in frames])
+    outs = [np.full((h, w, 4), SENTINEL, np.float32) if on else None for on in want[:2]]
+    outs.append(np.full((h, w), 255, np.uint8) if want[2] else None)
+    rc = lib.rs_pass_robust(ptrs, len(frames), w, h, gamma, A.RS_ROBUST_TRIM_AUTO if trim is None else trim,
+                            *[None if o is None else o.ctypes.data for o in outs])
+    assert rc == 0, lib.rs_last_error()
+    return outs
+
+
 def test_host_entry_equals_device_entry(gpu, pass_frames):
     for size in SIZES:
         for k, gamma, trim in ((3, 1, None), (16, 1, 0.1), (64, 0, None)):
@@ -200,6 +217,15 @@ def test_host_entry_equals_device_entry(gpu, pass_frames):
             dmean, dvar, dtrimmed = run_robust(gpu, frames, gamma, trim)
             assert np.array_equal(_bits(mean), _bits(dmean)) and np.array_equal(_bits(var), _bits(dvar))
             assert trimmed.dtype == np.uint8 and np.array_equal(trimmed, dtrimmed)
+    # mean only, var only, with and without `trimmed`, on the 67 x 5 corner of the frames (no multiple of the block, the
+    # NaN and inf pixels inside), K = 3 and 5: neither a multiple of the rank loop's groups of four
+    small = [np.ascontiguousarray(f[:5, :67]) for f in pass_frames[SIZES[1]][:5]]
+    for k, gamma, trim in ((3, 1, None), (5, 0, 0.25)):
+        for want in ((True, True, True), (True, True, False), (True, False, False), (False, True, True),
+                     (True, False, True), (False, True, False)):
+            host, dev = host_robust(small[:k], gamma, trim, want), run_robust(gpu, small[:k], gamma, trim, want)
+            for on, a, b in zip(want, host, dev):
+                assert (a is None and b is None) if not on else np.array_equal(_bits(a), _bits(b)), (k, want)
 
 
 def test_outputs_through_denoise_var(gpu, pass_frames):

@@ -84,6 +84,32 @@ def test_noise_map_kernel_matches_restatement(gpu):
 
 
 @pytest.mark.gpu
+def test_noise_map_host_entry_equals_device_entry(gpu):
+    """rs_noise_map with and without `redo` and `stats` on a 67 x 5 frame (no multiple of the block): what it writes is
+    what the device entry writes"""
+    torch = gpu
+    h, w = 5, 67
+    rng = np.random.default_rng(9)
+    px = rng.uniform(0, 1, (h, w, 4)).astype(np.float32) ** 3
+    px[rng.uniform(size=(h, w)) < 0.5] = px[0, 0]
+    thr = float(np.median(R.calc_noise(px)))  # (335 pixels: about half of the map is set)
+    lib = A.load()
+    d, d_redo, d_st = torch.from_numpy(px).cuda(), torch.zeros((h, w), dtype=torch.uint8, device="cuda"), A.rs_noise_stats()
+    assert lib.rs_noise_map_device(d.data_ptr(), w, h, thr, d_redo.data_ptr(), None, d_st) == 0
+    assert 0 < d_st.count < h * w and int(d_redo.sum()) == d_st.count
+    for want_redo in (True, False):
+        for want_stats in (True, False):
+            redo, st = np.full((h, w), 255, np.uint8), A.rs_noise_stats()
+            rc = lib.rs_noise_map(px.ctypes.data, w, h, thr, redo.ctypes.data if want_redo else None,
+                                  st if want_stats else None)
+            assert rc == 0, lib.rs_last_error()
+            if want_redo:
+                assert np.array_equal(redo, d_redo.cpu().numpy())
+            if want_stats:
+                assert (st.min, st.max, st.count) == (d_st.min, d_st.max, d_st.count)
+
+
+@pytest.mark.gpu
 def test_combine_kernel_matches_restatement(gpu):
     torch = gpu
     rng = np.random.default_rng(8)

@@ -1,18 +1,16 @@
 #!/bin/bash
-# dev: VGPRs / scratch / occupancy of the kernels of one unit of rs_kernels.hip (or of rs_denoise.hip: unit `denoise`;
-# of rs_denoise_var.hip: unit `denoise_var`; of rs_adaptive.hip: unit `adaptive`; of rs_robust.hip: unit `robust`) whose names match a pattern, compiled with exactly the flags raysnail_amd/csrc/Makefile gives that unit (its
-# unit-flags-<unit> target).
-# usage: tools/regs.sh <pattern> <unit: common | 0 .. 6 | denoise | denoise_var | adaptive | robust> [extra hipcc flags ...]
+# dev: VGPRs / scratch / occupancy of the kernels of one kernel unit (a unit of rs_kernels.hip, or one of the frame
+# operators' units rs_denoise.hip, rs_denoise_var.hip, rs_adaptive.hip, rs_robust.hip: tools/unit_src.sh) whose names
+# match a pattern, compiled with exactly the flags raysnail_amd/csrc/Makefile gives that unit (its unit-flags-<unit>
+# target).
+# usage: tools/regs.sh <pattern> <unit> [extra hipcc flags ...]
 # one line per kernel: VGPRs scratch-bytes waves/SIMD name
 set -eu
 R=$(cd "$(dirname "$0")/.." && pwd)
-[ $# -ge 2 ] || { echo "usage: $0 <pattern> <unit: common | 0 .. 6 | denoise | denoise_var | adaptive | robust> [extra hipcc flags ...]" >&2; exit 2; }
+. "$R/tools/unit_src.sh"
+[ $# -ge 2 ] || { echo "usage: $0 <pattern> <unit: $UNITS_USAGE> [extra hipcc flags ...]" >&2; exit 2; }
 pat=$1; unit=$2; shift 2
-src=rs_kernels.hip
-[ "$unit" = denoise ] && src=rs_denoise.hip
-[ "$unit" = denoise_var ] && src=rs_denoise_var.hip
-[ "$unit" = adaptive ] && src=rs_adaptive.hip
-[ "$unit" = robust ] && src=rs_robust.hip
+src=$(unit_src "$unit")
 HIPCC=${HIPCC:-/opt/rocm/bin/hipcc}
 flags=$(make -s --no-print-directory -C "$R/raysnail_amd/csrc" unit-flags-$unit)
 tmp=$(mktemp -d)
