@@ -655,6 +655,17 @@ int rs_probe_samples(rs_scene* s, const rs_camera_desc* cam, const rs_render_set
  * RS_E_INVALID. Diagnostic (shading parity against the oracle on exact inputs); additive extension of ABI 6. */
 int rs_probe_shade(rs_scene* s, const double* rows, uint32_t n, uint64_t seed, double* out);
 
+/* The camera sample alone (painter.rs:133-139, :167-170 and camera.rs:37-85), through the scene mode's own compile
+ * of the code every render kernel calls. xys: n triples of uint32 = [pixel x, pixel y, sample index below
+ * floor(sqrt(st->samples))^2]; st gives samples, seed and pass. centres == 0: the jittered sample rs_render draws;
+ * otherwise the stratum centre rs_render_features[_specular] uses (no jitter draw: the ray is drawn from the start
+ * of the sample's stream). out: n*11 doubles = [origin.xyz, direction.xyz, time, the four RNG state words after the
+ * sample]. Any camera rs_render accepts is accepted; a pixel outside the frame or a sample index beyond the
+ * stratum grid is RS_E_INVALID. Diagnostic (camera parity against the oracle on degenerate cameras); additive
+ * extension of ABI 6. */
+int rs_probe_camera(rs_scene* s, const rs_camera_desc* cam, const rs_render_settings* st, const uint32_t* xys, uint32_t n,
+                    int32_t centres, double* out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -59,6 +59,9 @@ def load(path: str = LIB_PATH) -> C.CDLL:
                                  C.POINTER(C.c_double)]
     lib.orc_camera_ray.argtypes = [C.POINTER(A.rs_camera_desc), C.c_double, C.c_double, C.c_uint64,
                                    C.POINTER(C.c_double)]
+    lib.orc_camera_sample.argtypes = [C.POINTER(A.rs_camera_desc), C.POINTER(A.rs_render_settings), C.c_void_p,
+                                      C.c_uint32, C.c_int32, C.c_void_p]
+    lib.orc_camera_sample.restype = C.c_int
     lib.orc_scatter.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_uint64,
                                 C.POINTER(C.c_double)]
     lib.orc_scatter.restype = C.c_int
@@ -164,6 +167,17 @@ class OracleScene:
         _check(self.lib, self.lib.orc_shade_level(self.h, rows.ctypes.data, len(rows), seed, out.ctypes.data), "orc_")
         return out
 
+
+def camera_sample(cam: A.rs_camera_desc, st: A.rs_render_settings, xys: np.ndarray, centres: bool) -> np.ndarray:
+    """The camera sample alone (orc_camera_sample): xys (n, 3) uint32 = pixel x, y, sample; returns (n, 11) doubles =
+    origin, direction, time, the four RNG words after the sample. centres: the feature buffers' stratum centres."""
+    lib = load()
+    xys = np.ascontiguousarray(xys, dtype=np.uint32)
+    assert xys.ndim == 2 and xys.shape[1] == 3
+    out = np.full((len(xys), 11), -7.0)
+    _check(lib, lib.orc_camera_sample(C.byref(cam), C.byref(st), xys.ctypes.data, len(xys), int(bool(centres)),
+                                      out.ctypes.data), "orc_")
+    return out
 
 
 def rtow_balls(seed: int = 7) -> np.ndarray:

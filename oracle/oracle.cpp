@@ -1602,6 +1602,35 @@ void orc_camera_ray(const rs_camera_desc* cd, double u, double v, uint64_t rng_s
     out[0] = r.origin.x; out[1] = r.origin.y; out[2] = r.origin.z;
     out[3] = r.direction.x; out[4] = r.direction.y; out[5] = r.direction.z; out[6] = r.time;
 }
+// The camera sample alone, for n (x, y, sample) triples: orc_sample_radiance's first lines up to Camera::ray
+// (centres == 0), or the stratum centre of the feature buffers (tests/features_ref.py camera_rays: both jitter terms
+// 0.5 and no jitter draw). out: n*11 doubles = [origin, direction, time, the RNG's four words after the sample].
+int orc_camera_sample(const rs_camera_desc* cd, const rs_render_settings* st, const uint32_t* xys, uint32_t n,
+                      int32_t centres, double* out) {
+    if (!cd || !st || !xys || !out) return fail(RS_E_INVALID, "null argument");
+    if (cd->width == 0 || cd->height == 0) return fail(RS_E_INVALID, "empty image");
+    Camera cam(*cd);
+    uint32_t sqrt_spp = (uint32_t)std::floor(std::sqrt((double)st->samples));
+    for (uint32_t i = 0; i < n; ++i) {
+        uint32_t x = xys[3 * (size_t)i], y = xys[3 * (size_t)i + 1], sample = xys[3 * (size_t)i + 2];
+        if (x >= cd->width || y >= cd->height || (uint64_t)sample >= (uint64_t)sqrt_spp * sqrt_spp)
+            return fail(RS_E_INVALID, "pixel or sample outside the frame");
+        uint32_t sj = sample / sqrt_spp, si = sample % sqrt_spp;
+        size_t pix = (size_t)y * cd->width + x;
+        FastRng rng = FastRng::seed_from_u64(stream_key(st->seed, st->pass, pix, sample));
+        double jx = centres ? 0.5 : rng.gen();
+        double jy = centres ? 0.5 : rng.gen();
+        double xo = (double)x + ((double)si + jx) / (double)sqrt_spp;
+        double yo = (double)y + ((double)sj + jy) / (double)sqrt_spp;
+        double hgt = (double)cd->height;
+        Ray r = cam.ray(xo / (double)cd->width, (hgt - 1.0 - yo) / hgt, rng);
+        double* o = out + 11 * (size_t)i;
+        o[0] = r.origin.x; o[1] = r.origin.y; o[2] = r.origin.z;
+        o[3] = r.direction.x; o[4] = r.direction.y; o[5] = r.direction.z; o[6] = r.time;
+        o[7] = (double)rng.x; o[8] = (double)rng.y; o[9] = (double)rng.z; o[10] = (double)rng.w;
+    }
+    return RS_OK;
+}
 // Material::scatter probe on a synthetic hit. in: ray o,d,time; hit p,n,t1,outside. out:
 // [ok, skip, has_ray, cr, cg, cb, rox, roy, roz, rdx, rdy, rdz, pdf_dir_x, pdf_dir_y, pdf_dir_z, pdf_value]
 int orc_scatter(orc_scene* s, int32_t mat, const double ray_in[7], const double hit_in[8], uint64_t rng_seed, double out[16]) {

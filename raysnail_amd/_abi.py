@@ -249,6 +249,9 @@ def load() -> C.CDLL:
     lib.rs_probe_samples.restype = C.c_int
     lib.rs_probe_shade.argtypes = [VP, VP, C.c_uint32, C.c_uint64, VP]
     lib.rs_probe_shade.restype = C.c_int
+    lib.rs_probe_camera.argtypes = [VP, C.POINTER(rs_camera_desc), C.POINTER(rs_render_settings), VP, C.c_uint32,
+                                    C.c_int32, VP]
+    lib.rs_probe_camera.restype = C.c_int
     lib.rs_render.argtypes = [VP, C.POINTER(rs_camera_desc), C.POINTER(rs_render_settings), VP, VP,
                               C.POINTER(rs_render_stats)]
     lib.rs_render_device.argtypes = [VP, C.POINTER(rs_camera_desc), C.POINTER(rs_render_settings), VP, VP, VP,
@@ -297,7 +300,7 @@ EXPORTED_SYMBOLS = [
     "rs_denoise_device", "rs_denoise",
     "rs_pass_moments_device", "rs_pass_moments", "rs_pass_robust_device", "rs_pass_robust",
     "rs_denoise_var_device", "rs_denoise_var",
-    "rs_probe_world_hit", "rs_probe_samples", "rs_probe_shade",
+    "rs_probe_world_hit", "rs_probe_samples", "rs_probe_shade", "rs_probe_camera",
 ]
 
 # every symbol include/raysnail_adaptive.h declares (checked by tests/test_adaptive_abi.py)

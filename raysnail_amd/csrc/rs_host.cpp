@@ -1416,12 +1416,14 @@ void ensure_stack_overflow(const rs_scene* s, Replica& R, uint64_t threads) {
 
 // a static scene's path records carry (item, level) in ray_o.w (rs_kernels.hip store_path; RS_NO_TAGW: the tag
 // array, for A/B)
-uint32_t tag_in_ray(const SceneRef& s) {
+// Only under a finite shutter: every time shutter * gen() is then finite and c + 0 * t is c; a time of inf or NaN
+// makes the reference miss every sphere (ray_consts), so it has to stay in the record.
+uint32_t tag_in_ray(const SceneRef& s, const DCamera& cam) {
 #ifdef RS_NO_TAGW
-    (void)s;
+    (void)s; (void)cam;
     return 0u;
 #else
-    return s.host->moving == 0 ? 1u : 0u;
+    return s.host->moving == 0 && std::isfinite(cam.shutter) ? 1u : 0u;
 #endif
 }
 
@@ -1949,7 +1951,7 @@ void StreamFrame::iteration(uint32_t l, uint64_t t) {
     const LaneSched& ln = f.lane[l];
     const hipStream_t cs = L.lane[l];
     WfState WS = L.lane_ws[l];
-    WS.tagw = tag_in_ray(c.ds);
+    WS.tagw = tag_in_ray(c.ds, c.dc);
     WS.counts = L.d_counts + ln.cnt_off;
     QEnt** qd = L.d_qptrs[l];
     const uint32_t n_new = ln.n_new(t);
@@ -2206,7 +2208,7 @@ void enqueue_batched(const rs_scene* s, const rs_render_settings* st, const Fram
             for (uint64_t c0 = 0; c0 < pp.n_items; c0 += chunk, ++chunk_i, lane = (lane + 1) % lanes) {
                 const uint32_t n = (uint32_t)std::min<uint64_t>(chunk, pp.n_items - c0);
                 WfState WS = L.lane_ws[lane];
-                WS.tagw = tag_in_ray(c.ds);
+                WS.tagw = tag_in_ray(c.ds, c.dc);
                 WS.counts = L.d_counts + chunk_i * (D + 1);
                 const hipStream_t cs = L.lane[lane];
                 // a pixel mask: k_wf_gen compacts the live samples into set 0's shards (counts from zero)
@@ -2343,7 +2345,7 @@ void render_enqueue(const rs_scene* s, Replica& R, const rs_camera_desc* cam, co
     c.d_out = d_out;
     c.outs = outs;
     c.outs_after = outs_after;
-    P.rec_bytes = tag_in_ray(c.ds) ? 96u : 104u;
+    P.rec_bytes = tag_in_ray(c.ds, c.dc) ? 96u : 104u;
     P.kind = !wavefront ? Scheme::Mega : streaming ? Scheme::Streaming : Scheme::Batched;
     P.n_frames = n_frames;
     P.n_pix = n_pix;
@@ -3349,6 +3351,35 @@ int rs_probe_shade(rs_scene* s, const double* rows, uint32_t n, uint64_t seed, d
         HIP_OK(hipMemcpy(out, dout, bytes, hipMemcpyDeviceToHost));
         (void)hipFree(dr);
         (void)hipFree(dout);
+    });
+}
+
+int rs_probe_camera(rs_scene* s, const rs_camera_desc* cam, const rs_render_settings* st, const uint32_t* xys, uint32_t n,
+                    int32_t centres, double* out) {
+    return run([&] {
+        S(s);
+        if (!cam || !st || !xys || !out) throw Error(RS_E_INVALID, "null argument");
+        if (!s->committed) throw Error(RS_E_STATE, "scene not committed");
+        if (cam->width == 0 || cam->height == 0) throw Error(RS_E_INVALID, "empty image");
+        const uint32_t sq = (uint32_t)std::floor(std::sqrt((double)st->samples));
+        for (uint32_t i = 0; i < n; ++i) {
+            const uint32_t* q = xys + 3 * (size_t)i;
+            if (q[0] >= cam->width || q[1] >= cam->height) throw Error(RS_E_INVALID, "pixel outside the frame");
+            if ((uint64_t)q[2] >= (uint64_t)sq * sq) throw Error(RS_E_INVALID, "sample index beyond floor(sqrt(samples))^2");
+        }
+        if (s->reps.empty()) throw Error(RS_E_STATE, "scene committed without devices (host-only build)");
+        Replica& R = *s->reps[0];
+        DeviceGuard g(R.device);
+        PathParams pp{};
+        pp.n_pix_local = cam->width * cam->height; pp.width = cam->width; pp.height = cam->height;
+        pp.row_begin = 0; pp.row_step = 1; pp.sqrt_spp = sq; pp.depth = st->depth;
+        pp.key_base = splitmix64_h(splitmix64_h(st->seed) ^ (uint64_t)st->pass);
+        const size_t in_bytes = (size_t)n * 3 * sizeof(uint32_t), out_bytes = (size_t)n * 11 * sizeof(double);
+        const DeviceMem din = device_alloc(in_bytes + 8), dout = device_alloc(out_bytes + 8);
+        HIP_OK(hipMemcpy(din.get(), xys, in_bytes, hipMemcpyHostToDevice));
+        HIP_OK(launch_probe_camera(make_camera(*cam), pp, static_cast<const uint32_t*>(din.get()), n, centres != 0,
+                                   static_cast<double*>(dout.get()), s->scene_mode, nullptr));
+        HIP_OK(hipMemcpy(out, dout.get(), out_bytes, hipMemcpyDeviceToHost));
     });
 }
 

@@ -154,6 +154,9 @@ hipError_t launch_probe_sample(const SceneRef& s, const DCamera& c, const PathPa
 // one shade_step per row on a synthetic hit record (k_probe_shade<sm>: the scene mode's own shading)
 hipError_t launch_probe_shade(const SceneRef& s, const double* rows, uint32_t n, uint64_t key_base, double* out, int sm,
                               hipStream_t st);
+// the camera sample of n (x, y, sample) triples (k_probe_camera<sm>: the scene mode's own compile of camera_ray)
+hipError_t launch_probe_camera(const DCamera& c, const PathParams& p, const uint32_t* xys, uint32_t n, int centres,
+                               double* out, int sm, hipStream_t st);
 hipError_t launch_path_mega(const SceneRef& s, const DCamera& c, const PathParams& p, int sm, double* rad,
                             unsigned long long* seg_counters, uint32_t max_blocks, hipStream_t st);
 // bounce-synchronous unsorted wavefront (flat / rich scenes): camera rays of a chunk, then per bounce

@@ -19,6 +19,7 @@
 
 #include "rs_device.h"
 #include "rs_internal.h"
+#include "rs_gen_perm.h"
 
 // Translation units (Makefile): the scene-mode templates of the path kernels are compiled once per
 // mode, in parallel. RS_TU undefined: everything in one unit (tools/regs.sh, build_variant.sh);
@@ -296,6 +297,10 @@ __device__ __forceinline__ bool sphere_t_trav(const DSphere& s, const Ray& r, do
 
 // Per-ray constants of the leaf tests, computed once per traversal: inv = 1 / d (the value
 // AABB::hit computes per node, aabb.rs:24) and a = |d|^2 (Sphere::hit's `a`, sphere.rs:88).
+// sphere_t_trav skips center_at for a sphere without speed because c + 0 * t is c -- for a finite t. At t = +-inf
+// or NaN (a non-finite shutter) sphere.rs:50-52 gives every sphere a NaN centre and Sphere::hit misses. So `a`
+// carries the time's class: time - time is +0 for a finite time, which leaves |d|^2 >= +0 bit for bit, and NaN
+// otherwise, which makes every sphere_t_trav discriminant NaN and the leaf a miss, as in the reference.
 struct RayC {
     V3 inv;
     double a;
@@ -303,7 +308,7 @@ struct RayC {
 __device__ __forceinline__ RayC ray_consts(const Ray& r) {
     RayC c;
     c.inv = v3(1.0 / r.d.x, 1.0 / r.d.y, 1.0 / r.d.z);
-    c.a = len2(r.d);
+    c.a = len2(r.d) + (r.time - r.time);
     return c;
 }
 // The same constants computed where this is called: the direction goes through an empty asm first, so
@@ -314,7 +319,7 @@ __device__ __forceinline__ RayC ray_consts_here(const Ray& r) {
     asm volatile("" : "+v"(d.x), "+v"(d.y), "+v"(d.z));
     RayC c;
     c.inv = v3(1.0 / d.x, 1.0 / d.y, 1.0 / d.z);
-    c.a = len2(d);
+    c.a = len2(d) + (r.time - r.time);
     return c;
 }
 
@@ -1174,7 +1179,8 @@ __device__ __forceinline__ void unpack_u32x2(double v, uint32_t& lo, uint32_t& h
 }
 // tw (WfState::tagw): the scene has no moving sphere, so a path's time is never read (a static sphere's centre
 // is c + 0 * t = c for any finite t >= 0, sphere.rs center_at), and its record carries (item, level) in ray_o.w
-// instead of the tag array: 8 B less each way per record (the shading is bound by its record traffic)
+// instead of the tag array: 8 B less each way per record (the shading is bound by its record traffic). The host
+// sets it only under a finite shutter (tag_in_ray): a non-finite time must reach ray_consts.
 __device__ __forceinline__ Ray load_ray(const WfSet& W, uint32_t p, bool tw = false, uint2* tag = nullptr) {
     const D4 a = W.ray_o[p], b = W.ray_d[p];
     Ray r;
@@ -1288,71 +1294,9 @@ __device__ __forceinline__ bool camera_sample(const DCamera& C, const PathParams
     return camera_sample(C, P, P.key_base, item, r, rng);
 }
 
-// Camera-ray order: the i-th camera sample a launch traces is item gen_perm(i) of its batch (whole
-// sample planes). A wave traces SP samples of each of 64 / SP lattice pixels: the batch's planes are cut into
-// groups of RS_PIX_SAMPLES planes and the rest into groups of decreasing powers of two (15 planes: 8, 4, 2, 1),
-// and inside a group of SP planes the i-th sample is plane i % SP of pixel i / SP in the pixels' tile order. The
-// camera rays of one pixel differ by the sub-pixel jitter and the lens disk only, so a wave of one pixel's
-// samples walks nearly one ray's nodes, and its hits, scattered rays and shading records stay together in the
-// later iterations' queues. Against one sample plane per wave (round 6): 32 samples of 2 pixels per wave, bench
-// frame 6.344 -> 6.212 ms, N = 8 share 0.900 -> 0.843 ms; 64 / 16 / 8 samples 6.260 / 6.226 / 6.232 ms; a C3-shaped
-// frame 41.6 -> 40.8 ms; C4, C5, C2 and X1 shapes equal (profiles/r6/ab/pix_samples_r7c.txt, _scenes_r7c.jsonl).
-// The pixels are visited in TW x TH tiles (TW * TH = 64 / SP; with one sample per pixel a 64 x 1 row strip spans
-// 8x the angle of an 8 x 8 tile -- bench frame 10.21 -> 9.89 ms in round 2), the pixels outside the whole tiles
-// after them in row-major order. Pure scheduling: rad[] is indexed by item, so the frame does not depend on it. A batch that is not whole planes keeps the identity order.
-#ifndef RS_PIX_SAMPLES
-#define RS_PIX_SAMPLES 32u
-#endif
+// Camera-ray order: the i-th camera sample a launch traces is item gen_perm(i) of its batch (rs_gen_perm.h).
 __device__ __forceinline__ uint32_t gen_perm(uint32_t i, uint64_t item0, uint32_t n, const PathParams& P) {
-    const uint32_t npl = P.n_pix_local, W = P.width;
-    if ((item0 % npl) != 0 || (n % npl) != 0) return i;
-    constexpr uint32_t M = RS_PIX_SAMPLES;  // a power of two <= 64
-    const uint32_t planes = n / npl, nfull = planes / M;
-    uint32_t SP = M, p0, r;  // i's group: its planes, first plane, and i's index inside it
-    if (i < nfull * M * npl) {
-        const uint32_t g = i / (M * npl);
-        p0 = g * M;
-        r = i - g * (M * npl);
-    } else {
-        p0 = nfull * M;
-        r = i - p0 * npl;
-        uint32_t left = planes - p0;  // 1 .. M - 1
-        SP = 1u << (31u - __clz(left));
-        while (r >= SP * npl) {
-            r -= SP * npl;
-            p0 += SP;
-            left -= SP;
-            SP = 1u << (31u - __clz(left));
-        }
-    }
-    const uint32_t TP = 64u / SP;  // pixels per wave
-    // A lattice with row step k (a strong-scaled share: rows r, r + k, ...) puts TH lattice rows
-    // TH * k screen rows apart: keep the tile near square on screen (64-pixel tiles: step >= 8: 16 x 4,
-    // 4-7: 32 x 2, 2-3: 16 x 4; step 1: 8 x 8)
-    uint32_t TH = 1u << ((31u - __clz(TP)) / 2);
-#ifndef RS_SHARE_TH8
-#define RS_SHARE_TH8 4u  // lattice rows per tile at row step >= 8 (16 x 4 lattice = 16 x 25 screen px at step 8; 64 x 1: N = 8 share 0.9416 -> 0.9313 ms, 32 x 2: 0.9342; profiles/r6/ab/variants_r6c_leaf2_th.txt)
-#endif
-    if (P.row_step > 1) TH = min(TH, P.row_step >= 8 ? RS_SHARE_TH8 : P.row_step >= 4 ? 2u : 4u);
-    const uint32_t TW = TP / TH;
-    const uint32_t s = p0 + r % SP;  // sample plane
-    uint32_t q = r / SP, pl;         // the pixel's position in the tile order
-    const uint32_t R = npl / W, Wt = W - W % TW, Rt = R - R % TH, nt = Wt * Rt;
-    if (q < nt) {
-        const uint32_t t = q / TP, k = q % TP, tpr = Wt / TW;
-        const uint32_t ty = t / tpr, tx = t - ty * tpr;
-        pl = (ty * TH + k / TW) * W + tx * TW + k % TW;
-    } else {
-        q -= nt;  // the right strip of the tiled rows, then the rows below
-        const uint32_t rw = W - Wt;
-        if (q < rw * Rt) {
-            const uint32_t lr = q / rw;
-            pl = lr * W + Wt + (q - lr * rw);
-        } else {
-            pl = Rt * W + (q - rw * Rt);
-        }
-    }
-    return s * npl + pl;
+    return gen_perm_item(i, item0, n, P.n_pix_local, P.width, P.row_step);
 }
 
 // The camera sample behind the streaming iteration's injected record jg (0-based among its injections):
@@ -2327,6 +2271,34 @@ __global__ __launch_bounds__(kBlock) void k_probe_shade(const DScene* __restrict
     o[14] = (double)rng.x; o[15] = (double)rng.y; o[16] = (double)rng.z; o[17] = (double)rng.w;
 }
 
+// Diagnostic: the camera sample alone (tests/ camera parity on degenerate cameras; the oracle's orc_camera_sample).
+// Row i: xys[3 i ..] = pixel x, y and sample index. centres == 0: camera_sample_xy, the render kernels' jittered
+// sample; otherwise the stratum centre of k_features / k_features_spec (no jitter draw: the ray is drawn from the
+// start of the sample's stream). out[11 i ..] = o(3), d(3), time, the four RNG state words after the sample.
+template <int SM>
+__global__ __launch_bounds__(kBlock) void k_probe_camera(DCamera C, PathParams P, const uint32_t* __restrict__ xys, uint32_t n,
+                                                        int centres, double* __restrict__ out) {
+    const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
+    if (i >= n) return;
+    const uint32_t x = xys[3 * (size_t)i], y = xys[3 * (size_t)i + 1], s = xys[3 * (size_t)i + 2];
+    Ray r;
+    Rng rng;
+    if (!centres) {
+        camera_sample_xy(C, P, P.key_base, x, y, s, r, rng);
+    } else {  // k_features' statements
+        const uint64_t pix = (uint64_t)y * P.width + x;
+        const double sq = (double)P.sqrt_spp, hh = (double)P.height;
+        rng.seed_from_u64(splitmix64(splitmix64(P.key_base ^ pix) ^ (uint64_t)s));
+        const uint32_t si = s % P.sqrt_spp, sj = s / P.sqrt_spp;
+        const double xo = (double)x + ((double)si + 0.5) / sq;
+        const double yo = (double)y + ((double)sj + 0.5) / sq;
+        r = camera_ray(C, xo / (double)P.width, (hh - 1.0 - yo) / hh, rng);
+    }
+    double* o = out + 11 * (size_t)i;
+    o[0] = r.o.x; o[1] = r.o.y; o[2] = r.o.z; o[3] = r.d.x; o[4] = r.d.y; o[5] = r.d.z; o[6] = r.time;
+    o[7] = (double)rng.x; o[8] = (double)rng.y; o[9] = (double)rng.z; o[10] = (double)rng.w;
+}
+
 #if !defined(RS_TU) || RS_TU == 5 || RS_TU == 6
 // First-hit feature buffers: per pixel the mean over its N samples of the camera ray's first hit --
 // albedo and coverage into one RGBA f32 frame, shading normal and depth into another. Sample s of pixel p is the
@@ -2723,7 +2695,9 @@ hipError_t launch_cam_cand_build(const SceneRef& s, const DCamera& c, const Path
                              double* rad, uint32_t blocks, hipStream_t st), (s, w, bounce, depth, n_items, rad, blocks, st)) \
     X(hipError_t, wf_occupancy, (int* e, int* sh), (e, sh))                                                    \
     X(hipError_t, probe_shade, (const SceneRef& s, const double* rows, uint32_t n, uint64_t key_base, double* out,  \
-                                hipStream_t st), (s, rows, n, key_base, out, st))
+                                hipStream_t st), (s, rows, n, key_base, out, st))                               \
+    X(hipError_t, probe_camera, (const DCamera& c, const PathParams& p, const uint32_t* xys, uint32_t n, int centres, \
+                                 double* out, hipStream_t st), (c, p, xys, n, centres, out, st))
 #define RS_SORTED_LAUNCHERS(X)                                                                                 \
     X(hipError_t, wfs_extend, (const SceneRef& s, const DCamera& c, const PathParams& p, const WfState& w,       \
                                QEnt* const* queues, uint32_t it, const InjParams& inj, double* rad, uint32_t blocks, \
@@ -2754,6 +2728,15 @@ hipError_t probe_shade_sm(const SceneRef& s, const double* rows, uint32_t n, uin
     const uint32_t blocks = (n + kBlock - 1) / kBlock;
     if (!blocks) return hipSuccess;
     hipLaunchKernelGGL(k_probe_shade<SMC>, dim3(blocks), dim3(kBlock), 0, st, s.dev, rows, n, key_base, out);
+    return hipGetLastError();
+}
+
+template <int SMC>
+hipError_t probe_camera_sm(const DCamera& c, const PathParams& p, const uint32_t* xys, uint32_t n, int centres, double* out,
+                           hipStream_t st) {
+    const uint32_t blocks = (n + kBlock - 1) / kBlock;
+    if (!blocks) return hipSuccess;
+    hipLaunchKernelGGL(k_probe_camera<SMC>, dim3(blocks), dim3(kBlock), 0, st, c, p, xys, n, centres, out);
     return hipGetLastError();
 }
 
@@ -2906,6 +2889,12 @@ hipError_t launch_probe_sample(const SceneRef& s, const DCamera& c, const PathPa
 hipError_t launch_probe_shade(const SceneRef& s, const double* rows, uint32_t n, uint64_t key_base, double* out, int sm,
                               hipStream_t st) {
     RS_SM_DISPATCH(sm, return probe_shade_sm<SMC>(s, rows, n, key_base, out, st));
+    return hipErrorInvalidValue;
+}
+
+hipError_t launch_probe_camera(const DCamera& c, const PathParams& p, const uint32_t* xys, uint32_t n, int centres,
+                               double* out, int sm, hipStream_t st) {
+    RS_SM_DISPATCH(sm, return probe_camera_sm<SMC>(c, p, xys, n, centres, out, st));
     return hipErrorInvalidValue;
 }
 

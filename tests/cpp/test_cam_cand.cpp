@@ -11,6 +11,20 @@
 // pinhole, and a camera inside a large sphere. For the bench camera at most 6 % of the pixels with any candidate may
 // be marked overflow, so that the property cannot pass by overflowing everywhere.
 //
+// Cameras chosen against the criterion's own code (edge_cameras below): (R + rho) / |d| of the centre pixel just
+// below and just above the `wide` threshold 0.99, once with a lens (rho < R: the slope b[0] of piece 0 is negative)
+// and once through a pinhole with huge pixels (rho > R: b[0] positive, both pieces' k at the threshold); a lens
+// smaller than a pixel's footprint (0 < R < rho); focus negative; focus 0 (F == O: every beam has ok == 0); fov 180;
+// spheres centred exactly on O, exactly on a pixel's axis (h == 0) and of radius 0; and the RTIOW-shaped field with
+// the bench camera, both multiplied by 1e-6 and by 1e6.
+// Overflow shares, measured with this program (g++ -O2, x86-64) over the RTIOW-shaped field: bench 0.02 % (1 of
+// 5007 pixels with candidates), bench x 1e-6 0.02 % (1 of 5007), bench x 1e6 0.02 % (1 of 5007). The scaled scenes
+// are similar figures of the bench scene, so up to the criterion's absolute slack terms their share is the bench
+// camera's: each is capped at that measured share plus one percentage point, 1.02 % (kScaledCap). The cameras that
+// keep everything cannot be capped and are checked otherwise, over at most 8 spheres: where every beam is `wide`
+// ("all wide") every record must list every sphere; where every beam has ok == 0 ("focus 0") every record must be
+// marked overflow, which sends the pixel's rays to the tree walk.
+//
 // Stand-alone (no library): g++ -O2 -std=c++17 tests/cpp/test_cam_cand.cpp; prints "ok" last and exits 0.
 #include <cmath>
 #include <cstdint>
@@ -132,10 +146,23 @@ static std::vector<std::pair<uint32_t, uint32_t>> pick_pixels(uint32_t W, uint32
 
 // Every sphere hit by a ray of a pixel's family is in the pixel's record (or the record overflows). cap: the share of
 // the pixels with any candidate that may overflow, over the whole frame (negative: not checked).
-static void check_camera(const char* name, const Cam& c, const std::vector<Sph>& sph, double cap) {
+// keep_all: the camera is expected to keep every sphere in every pixel's record (every beam wide or unusable).
+static double check_camera(const char* name, const Cam& c, const std::vector<Sph>& sph, double cap, bool keep_all = false) {
     const CandCam cc = cand_camera(c.origin, c.lb, c.hf, c.vf, c.hu, c.vu, c.aperture, c.W, c.H);
     CHECK(cc.ok, "%s: camera not usable", name);
-    if (!cc.ok) return;
+    if (!cc.ok) return -1.0;
+    if (keep_all) {
+        CHECK(sph.size() <= kCandMax, "%s: a camera that keeps everything needs at most %u spheres", name, kCandMax);
+        for (uint32_t y = 0; y < c.H; ++y)
+            for (uint32_t x = 0; x < c.W; ++x) {
+                const CandBeam b = cand_beam(cc, x, y);
+                const Record r = build_record(cc, sph, x, y);
+                CHECK(!b.ok || b.wide, "%s: pixel (%u, %u) has a usable narrow beam", name, x, y);
+                // an unusable beam's record is marked overflow (the pixel's rays walk the tree); a wide one lists all
+                if (!b.ok) CHECK(r.overflow, "%s: pixel (%u, %u): ok == 0 and the record is not marked overflow", name, x, y);
+                else CHECK(!r.overflow && r.n == sph.size(), "%s: pixel (%u, %u) lists %u of %zu spheres", name, x, y, r.n, sph.size());
+            }
+    }
     CHECK(sph.size() <= kCandMaxEntries, "%s: too many spheres for a record", name);
     // the frame's statistics
     uint64_t with = 0, over = 0, sum = 0, mx = 0;
@@ -151,6 +178,7 @@ static void check_camera(const char* name, const Cam& c, const std::vector<Sph>&
     std::printf("%-14s %ux%u, %zu spheres: mean %.3f candidates per pixel (without overflow pixels), max %llu, overflow %.2f %% of %llu pixels with candidates\n",
                 name, c.W, c.H, sph.size(), (double)sum / (double)((uint64_t)c.W * c.H - over ? (uint64_t)c.W * c.H - over : 1),
                 (unsigned long long)mx, 100.0 * share, (unsigned long long)with);
+    if (keep_all && over == (uint64_t)c.W * c.H) return share;  // no record to check a ray against
     if (cap >= 0.0) CHECK(share <= cap, "%s: %.2f %% of the pixels with candidates overflow (cap %.2f %%)", name, 100.0 * share, 100.0 * cap);
 
     const double W = (double)c.W, H = (double)c.H;
@@ -194,6 +222,142 @@ static void check_camera(const char* name, const Cam& c, const std::vector<Sph>&
     std::printf("%-14s %llu rays, %llu sphere hits, %llu not listed; %llu of the picked pixels overflow\n", name,
                 (unsigned long long)rays, (unsigned long long)hits, (unsigned long long)missed, (unsigned long long)over_px);
     CHECK(rays > 0, "%s: every picked pixel overflows", name);
+    return share;
+}
+
+static std::vector<Sph> scaled(const std::vector<Sph>& s, double k) {
+    std::vector<Sph> o;
+    for (const Sph& q : s) o.push_back({{q.c[0] * k, q.c[1] * k, q.c[2] * k}, q.r * k});
+    return o;
+}
+
+// (R + rho) / |d| and (rho - R) / |d| of a pixel's beam
+static void beam_k(const Cam& c, uint32_t x, uint32_t y, double k[2], int* wide) {
+    const CandCam cc = cand_camera(c.origin, c.lb, c.hf, c.vf, c.hu, c.vu, c.aperture, c.W, c.H);
+    const CandBeam b = cand_beam(cc, x, y);
+    k[0] = b.b[0] * b.inv_len; k[1] = b.b[1] * b.inv_len;
+    *wide = b.wide;
+}
+
+// how many of the frame's beams are wide
+static uint32_t wide_beams(const Cam& c) {
+    const CandCam cc = cand_camera(c.origin, c.lb, c.hf, c.vf, c.hu, c.vu, c.aperture, c.W, c.H);
+    uint32_t n = 0;
+    for (uint32_t y = 0; y < c.H; ++y)
+        for (uint32_t x = 0; x < c.W; ++x) n += cand_beam(cc, x, y).wide ? 1u : 0u;
+    return n;
+}
+
+// Cameras at the edges of the criterion's own code, each over a handful of spheres around its beams (at most 8, so a
+// beam that keeps everything still gives a record to check) plus, where asked, the special spheres of pixel (px, py).
+static void edge_cameras() {
+    const double f0[3] = {0.0, 0.0, 0.0}, a0[3] = {0.0, 0.0, -1.0};
+    auto around = [](double dist) {  // six spheres in front of, beside and behind the lens
+        std::vector<Sph> s;
+        s.push_back({{0.1 * dist, 0.05 * dist, -dist}, 0.2 * dist});
+        s.push_back({{-0.6 * dist, 0.2 * dist, -1.5 * dist}, 0.3 * dist});
+        s.push_back({{0.9 * dist, -0.4 * dist, -0.7 * dist}, 0.25 * dist});
+        s.push_back({{0.0, 1.4 * dist, -0.2 * dist}, 0.3 * dist});
+        s.push_back({{0.3 * dist, -0.2 * dist, 1.2 * dist}, 0.4 * dist});    // behind the lens
+        s.push_back({{-2.0 * dist, 0.0, 0.1 * dist}, 0.5 * dist});
+        return s;
+    };
+    // ---- the wide threshold with a lens: rho < R, k[1] = (R + rho) / |d| of the centre pixel at 0.99 (1 -+ 2^-20) ----
+    for (int above = 0; above < 2; ++above) {
+        const uint32_t W = 33, H = 21;   // odd: pixel (16, 9) has u = 1 / 2 and v = (21 - 1.5 - 9) / 21 = 1 / 2
+        Cam c = make_cam(f0, a0, 20.0, 0.0, 1.0, W, H);
+        const CandCam cc = cand_camera(c.origin, c.lb, c.hf, c.vf, c.hu, c.vu, 0.0, W, H);
+        const CandBeam b = cand_beam(cc, 16, 9);
+        const double target = 0.99 * (above ? 1.0 + 0x1p-20 : 1.0 - 0x1p-20);
+        c.aperture = 2.0 * (target * b.len - cc.rho) / (1.0 + 0x1p-40);   // R = |aperture| / 2 * sqrt(1 + 0) * slack
+        double k[2]; int wide;
+        beam_k(c, 16, 9, k, &wide);
+        CHECK(wide == above && std::fabs(k[1] / 0.99 - 1.0) < 0x1p-19 && k[0] < 0.0 && std::fabs(k[0]) < 0.99,
+              "lens threshold %d: k %.17g %.17g wide %d", above, k[0], k[1], wide);
+        const uint32_t nw = wide_beams(c);
+        std::printf("%-14s k = %.9f / %.9f at the centre pixel, %u of %u beams wide\n", above ? "lens above" : "lens below", k[0], k[1], nw, W * H);
+        CHECK(above ? (nw > 0 && nw < W * H) : nw == 0, "lens threshold %d: %u wide beams", above, nw);  // |d| grows off-centre
+        check_camera(above ? "lens above" : "lens below", c, around(1.0), -1.0);
+    }
+    // ---- the wide threshold through a pinhole with huge pixels: R = 0 < rho, both pieces' k = rho / |d| ----
+    for (int above = 0; above < 2; ++above) {
+        const double target = 0.99 * (above ? 1.0 + 0x1p-20 : 1.0 - 0x1p-20);
+        double lo = 100.0, hi = 179.0;   // k of pixel (0, 0) of a 2 x 2 frame grows with the fov: bisect
+        Cam c;
+        for (int it = 0; it < 200; ++it) {
+            const double mid = 0.5 * (lo + hi);
+            c = make_cam(f0, a0, mid, 0.0, 1.0, 2, 2);
+            double k[2]; int wide;
+            beam_k(c, 0, 0, k, &wide);
+            if (k[1] < target) lo = mid; else hi = mid;
+        }
+        c = make_cam(f0, a0, above ? hi : lo, 0.0, 1.0, 2, 2);
+        double k[2]; int wide;
+        beam_k(c, 0, 0, k, &wide);
+        CHECK(wide == above && std::fabs(k[1] / 0.99 - 1.0) < 0x1p-19 && k[0] == k[1], "pinhole threshold %d: fov %.17g k %.17g %.17g wide %d",
+              above, above ? hi : lo, k[0], k[1], wide);
+        std::printf("%-14s fov %.12f, k = %.9f at pixel (0, 0), %u of 4 beams wide\n", above ? "pinhole above" : "pinhole below",
+                    above ? hi : lo, k[1], wide_beams(c));
+        check_camera(above ? "pinhole above" : "pinhole below", c, around(1.0), -1.0);
+    }
+    // ---- 0 < R < rho: a lens smaller than a pixel's footprint (b[0] > 0 with R != 0) ----
+    {
+        const Cam c = make_cam(f0, a0, 60.0, 1e-3, 2.0, 8, 5);
+        double k[2]; int wide;
+        beam_k(c, 4, 2, k, &wide);
+        CHECK(k[0] > 0.0 && k[0] < k[1] && !wide, "small lens: k %.17g %.17g", k[0], k[1]);
+        check_camera("small lens", c, around(2.0), -1.0);
+    }
+    // ---- clearly wide everywhere (aperture 4 at focus 1), and focus 0 (F == O: ok == 0): everything is kept ----
+    {
+        const Cam c = make_cam(f0, a0, 20.0, 4.0, 1.0, 16, 10);
+        CHECK(wide_beams(c) == 160, "aperture 4 at focus 1: %u of 160 beams wide", wide_beams(c));
+        check_camera("all wide", c, around(1.0), -1.0, true);
+        const Cam z = make_cam(f0, a0, 20.0, 0.5, 0.0, 16, 10);
+        const CandCam cc = cand_camera(z.origin, z.lb, z.hf, z.vf, z.hu, z.vu, z.aperture, z.W, z.H);
+        CHECK(cc.ok, "focus 0: the camera's fields are finite");
+        for (uint32_t y = 0; y < z.H; ++y)
+            for (uint32_t x = 0; x < z.W; ++x) CHECK(!cand_beam(cc, x, y).ok, "focus 0: pixel (%u, %u) has a usable beam", x, y);
+        check_camera("focus 0", z, around(1.0), -1.0, true);
+    }
+    // ---- focus negative: the footprint behind the lens, the rays run backwards through it ----
+    check_camera("focus -4", make_cam(f0, a0, 40.0, 0.25, -4.0, 32, 20), around(3.0), -1.0);
+    check_camera("focus -4 pin", make_cam(f0, a0, 40.0, 0.0, -4.0, 32, 20), around(3.0), -1.0);
+    // ---- fov 180: tan(pi / 2) = 1.6e16, a viewport 1e16 wide ----
+    {
+        const Cam c = make_cam(f0, a0, 180.0, 0.1, 1.0, 16, 10);
+        std::printf("%-14s %u of 160 beams wide\n", "fov 180", wide_beams(c));
+        check_camera("fov 180", c, around(1.0), -1.0);
+        std::vector<Sph> far = scaled(around(1.0), 1e15);   // spheres at the viewport's own scale
+        check_camera("fov 180 far", c, far, -1.0);
+    }
+    // ---- spheres centred exactly on O, exactly on a pixel's axis (h == 0), and of radius 0 ----
+    {
+        const double from[3] = {1.0, 0.5, 4.0}, at[3] = {0.0, 0.0, 0.0};
+        const Cam c = make_cam(from, at, 35.0, 0.05, 4.0, 32, 20);
+        const CandCam cc = cand_camera(c.origin, c.lb, c.hf, c.vf, c.hu, c.vu, c.aperture, c.W, c.H);
+        std::vector<Sph> s;
+        s.push_back({{from[0], from[1], from[2]}, 0.5});      // centre == O, the lens inside
+        s.push_back({{from[0], from[1], from[2]}, 0.01});     // centre == O, smaller than the lens
+        for (uint32_t k = 0; k < 3; ++k) {                    // on the axes of three pixels, before, at and past F
+            const uint32_t px[3] = {0, 16, 31}, py[3] = {0, 9, 19};
+            const double t[3] = {0.5, 1.0, 2.5};
+            const CandBeam b = cand_beam(cc, px[k], py[k]);
+            s.push_back({{b.o[0] + t[k] * b.d[0], b.o[1] + t[k] * b.d[1], b.o[2] + t[k] * b.d[2]}, 0.125});
+        }
+        s.push_back({{0.0, 0.0, 0.0}, 0.0});                  // radius 0: hit only when the discriminant is exactly 0
+        s.push_back({{0.25, 0.0, 0.5}, 0.0});
+        {
+            const CandBeam b = cand_beam(cc, 16, 9);
+            const Sph& q = s[3];
+            const double w[3] = {q.c[0] - b.o[0], q.c[1] - b.o[1], q.c[2] - b.o[2]};
+            const double cx = w[1] * b.d[2] - w[2] * b.d[1], cy = w[2] * b.d[0] - w[0] * b.d[2], cz = w[0] * b.d[1] - w[1] * b.d[0];
+            CHECK(cx == 0.0 && cy == 0.0 && cz == 0.0, "the sphere at F of pixel (16, 9) is off its axis: %g %g %g", cx, cy, cz);
+            CHECK(cand_sphere(b, s[0].c, s[0].r) && cand_sphere(b, s[1].c, s[1].r), "a sphere centred on O is rejected");
+            CHECK(cand_sphere(b, q.c, q.r), "the sphere on the axis is rejected");
+        }
+        check_camera("special", c, s, -1.0);
+    }
 }
 
 // the layout of RTIOW-13.1 (examples/common/scene.rs): ground, a 22 x 22 field of small spheres, three large ones, the light
@@ -227,7 +391,16 @@ int main(int argc, char** argv) {
         check_camera("bench (file)", bench, s, 0.06);
     }
     const std::vector<Sph> field = rtiow_like();
+    const double kScaledCap = 0.0002 + 0.01;  // the bench camera's measured share (header comment) + one percentage point
     check_camera("bench", bench, field, 0.06);
+    for (const double k : {1e-6, 1e6}) {
+        // a similar figure of the bench scene: its overflow share is the bench camera's, up to the criterion's absolute
+        // slack terms; the cap is the bench camera's measured share plus one percentage point
+        const double fk[3] = {from[0] * k, from[1] * k, from[2] * k};
+        const Cam sc = make_cam(fk, at, 20.0, 0.02 * k, 10.0 * k, 96, 60);
+        check_camera(k < 1.0 ? "bench x 1e-6" : "bench x 1e6", sc, scaled(field, k), kScaledCap);
+    }
+    edge_cameras();
     {
         // a wide lens in front of a cloud of spheres 0.5 - 3 units away
         const double f0[3] = {0.0, 0.0, 0.0}, a0[3] = {0.0, 0.0, -1.0};
