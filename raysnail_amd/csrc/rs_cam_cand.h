@@ -111,6 +111,34 @@ RS_CC_HD inline CandBeam cand_beam(const CandCam& c, uint32_t x, uint32_t y) {
     return b;
 }
 
+// The beam of every ray (1 - s) L + s Fq, s >= 0, with L in the ball (O, R) and Fq in the ball (F, rho): cand_beam()'s
+// fields for any such pair, with the same ok / wide rules (rs_light_cand.h: a cell of space and the light).
+RS_CC_HD inline CandBeam cand_beam_ball(const double O[3], double R, const double F[3], double rho) {
+    CandBeam b;
+    double l2 = 0.0;
+    bool fin = cand_finite(R) && cand_finite(rho);
+    for (int k = 0; k < 3; ++k) {
+        b.o[k] = O[k];
+        b.d[k] = F[k] - O[k];
+        l2 += b.d[k] * b.d[k];
+        fin = fin && cand_finite(O[k]) && cand_finite(F[k]);
+    }
+    b.len = sqrt(l2);
+    b.inv_len = 1.0 / b.len;
+    b.inv_len2 = 1.0 / l2;
+    b.R = fabs(R); b.rho = fabs(rho);
+    b.ok = fin && cand_finite(l2) && l2 > 0.0 && cand_finite(b.inv_len2);
+    b.b[0] = b.rho - b.R;
+    b.b[1] = b.R + b.rho;
+    b.wide = 0;
+    for (int piece = 0; piece < 2; ++piece) {
+        const double k = b.b[piece] * b.inv_len;
+        if (!(fabs(k) <= 0.99)) { b.wide = 1; b.kf[piece] = 0.0; continue; }
+        b.kf[piece] = k * b.inv_len / sqrt(1.0 - k * k);
+    }
+    return b;
+}
+
 // Can a ray of the beam touch the sphere (centre c, radius r)? Never false when g(s) <= 0 for some s >= 0; *along
 // (when given) receives the centre's parameter along the axis (the lists' order). A node's box goes through its
 // bounding sphere (centre, half diagonal).

@@ -816,6 +816,15 @@ void build_limg(rs_scene* s) {
     s->hs.blobs.push_back(std::move(b));
 }
 
+// Does the scene get cell records for its light-sample rays (light_cand, rs_internal.h)? cam_cand_scene's conditions
+// (asked while the scene is built: the tree's fields of `d` are set, its arrays not yet) and exactly one light.
+bool light_cand_scene(const rs_scene* s, const DScene& d) {
+    return light_cand(s->scene_mode, kExtCarried) && d.moving == 0 && d.root4 >= 0 && !s->ref_order &&
+           s->objs.size() <= kCandMaxEntries && s->stack_need <= kCandStack && s->lights.size() == 1;
+}
+
+bool try_malloc(void** p, size_t bytes);  // (below)
+
 // copy the staged scene to `device` as a new replica
 void upload_replica(rs_scene* s, int device) {
     std::unique_ptr<Replica> R(new Replica());
@@ -845,6 +854,19 @@ void upload_replica(rs_scene* s, int device) {
     R->n_cu = prop.multiProcessorCount;
     R->mem_total = (uint64_t)prop.totalGlobalMem;
     HIP_OK(wf_occupancy(s->scene_mode, &R->ext_bpc, &R->shade_bpc));
+    // the light-sample rays' cell records (rs_light_cand.h): built here, once per commit and replica, on the replica's
+    // stream and finished before the commit returns; a device without room for them renders without
+    if (R->ds.lgrid.cells) {
+        void* p = nullptr;
+        if (R->ds.lsphs && try_malloc(&p, (size_t)R->ds.lgrid.cells * sizeof(uint4))) {
+            R->dev.push_back(p);
+            R->ds.lcand = (const uint32_t*)p;
+            HIP_OK(launch_light_cand_build(R->ref(), (uint4*)p, R->stream));
+            HIP_OK(hipStreamSynchronize(R->stream));
+        } else {
+            R->ds.lgrid.cells = 0;
+        }
+    }
     s->reps.push_back(std::move(R));
 }
 
@@ -1223,6 +1245,21 @@ void build(rs_scene* s) {
             }
             stage(s, d.lsphs, lsphs);
         }
+    }
+    // the cell grid of the light-sample rays' candidate lists (rs_light_cand.h); the records are built per replica
+    d.lgrid = LightGrid{};
+    d.lcand = nullptr;
+    if (light_cand_scene(s, d) && lights.size() == 1 && s->objs[lights[0]].kind == PK_SPHERE) {
+        std::vector<double> c, r;
+        uint32_t light = 0;
+        for (size_t h = 0; h < s->objs.size(); ++h) {
+            if (s->objs[h].kind != PK_SPHERE) continue;
+            if ((int32_t)h == lights[0]) light = (uint32_t)r.size();
+            const DSphere& sp = spheres[prims[h].idx];
+            c.insert(c.end(), sp.c, sp.c + 3);
+            r.push_back(sp.r);
+        }
+        d.lgrid = light_grid_make(c.data(), r.data(), (uint32_t)r.size(), light);
     }
     if (s->scene_mode == kSmFlat) {
         std::vector<LTri> ltri(leaves.prims.size());

@@ -4,6 +4,7 @@
 #include <stdint.h>
 #include "rs_layout.h"
 #include "rs_cam_cand.h"
+#include "rs_light_cand.h"
 
 namespace rs {
 
@@ -215,6 +216,17 @@ constexpr bool cam_cand(int sm, int part) { return RS_CAM_CAND && sm == kSmSpher
 // scene is a spheres-mode one without motion on the near-first 4-wide tree, stack_need <= kCandStack (the caller's
 // checks: cam_cand_scene in rs_host.cpp)
 hipError_t launch_cam_cand_build(const SceneRef& s, const DCamera& c, const PathParams& p, uint4* cand, hipStream_t st);
+// The spheres mode's carried launch finds the hit of a light-sample ray (the front run of a carried set) among the
+// candidate spheres of the cell of space it starts in (one 16-byte record per cell of DScene::lgrid, rs_light_cand.h,
+// written once per commit by k_light_cand_build) instead of walking the tree: such a ray starts at a scatter point and
+// passes through the scene's one light, so what it can touch depends on its origin's cell and the scene only.
+// RS_LIGHT_CAND=0: the kernel that always walks and a host that builds no records, for A/B.
+#ifndef RS_LIGHT_CAND
+#define RS_LIGHT_CAND 1
+#endif
+constexpr bool light_cand(int sm, int part) { return RS_LIGHT_CAND && sm == kSmSpheres && part == kExtCarried; }
+// one record per cell of s.host->lgrid into cand[0, cells); the scene as for launch_cam_cand_build, with one light
+hipError_t launch_light_cand_build(const SceneRef& s, uint4* cand, hipStream_t st);
 hipError_t launch_wfs_extend(const SceneRef& s, const DCamera& c, const PathParams& p, const WfState& w,
                              QEnt* const* queues, uint32_t it, const InjParams& inj, double* rad, uint32_t blocks,
                              int part, int sm, hipStream_t st, hipEvent_t ev0 = nullptr, hipEvent_t ev1 = nullptr);

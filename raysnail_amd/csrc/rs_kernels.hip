@@ -1650,6 +1650,34 @@ __device__ __forceinline__ void lds_scene(const DScene* __restrict__ Sp, DScene&
     Sv.tf_fwd = (const DMat34*)(b + Sv.limg_off[LT_TF_FWD]);
     Sv.tf_inv = (const DMat34*)(b + Sv.limg_off[LT_TF_INV]);
 }
+// A candidate record in place of the walk (the camera part's lattice pixels, rs_cam_cand.h; the carried part's cells of
+// space, rs_light_cand.h): the walk's own leaf test on each entry in list order. Closest hit among spheres does not
+// depend on the order except where two spheres share the best t exactly, which the walk resolves
+// by its order. True: the list settled the ray -- bp the winner's prim (-1: none), t its t (RS_INF: none). False: an
+// overflow record (more than kCandMax candidates) or such a tie, the lane walks. Scenes with lists have no moving sphere.
+__device__ __forceinline__ bool cand_list_hit(const DScene& S, uint4 rec, const Ray& r, int& bp, double& t) {
+    if ((rec.x & 0xFFFFu) == kCandOverflow) return false;
+    const RayC rc = ray_consts(r);
+    double best = RS_INF, be = RS_INF;
+    int b = -1;
+    bool tie = false;
+    TravStat st;
+    // one copy of the leaf test; the record is shifted down an entry per pass (empty ones come in)
+    for (uint32_t k = 0; k < kCandMax; ++k) {
+        const uint32_t e = rec.x & 0xFFFFu;
+        if (e == kCandEmpty) break;
+        rec.x = (rec.x >> 16) | (rec.y << 16); rec.y = (rec.y >> 16) | (rec.z << 16);
+        rec.z = (rec.z >> 16) | (rec.w << 16); rec.w = (rec.w >> 16) | 0xFFFF0000u;
+        st.leaf();
+        test_sphere_leaf<true>(S, ld_sphere_s(S.lsphs, (int)e), (int)e, r, rc, 0.0001, best, be, b, &tie);
+    }
+    if (tie) return false;
+    st.store();
+    t = best;  // the winner's t
+    bp = (b >= 0 && S.lprim) ? S.lprim[b] : b;
+    return true;
+}
+
 // PART (rs_internal.h): kExtAll -- the carried paths and the injected camera samples in one launch;
 // kExtCarried / kExtCamera -- one of the two (an iteration then takes two launches): where the merged
 // kernel needs more registers than either alone (nest-2: 256 VGPRs + 2 AGPRs, one wave per SIMD,
@@ -1677,6 +1705,8 @@ __global__ __launch_bounds__(kBlock, ext_min_waves(SM, LOBJ, PART)) void k_wfs_e
     constexpr bool kFuse = cam_fused(SM, PART);
     // ... and finds them among the pixel's candidate spheres where the launch has the records (below)
     constexpr bool kCand = cam_cand(SM, PART);
+    // the spheres mode's carried launch: its light-sample rays among their cell's candidate spheres (below)
+    constexpr bool kLCand = light_cand(SM, PART);
     const uint32_t base0 = blockIdx.x * kBlock;
     for (uint32_t base = base0; base < n; base += gridDim.x * kBlock) {
         // thread -> record: the front run [0, nf), the back run from the set's end down, then the
@@ -1720,37 +1750,35 @@ __global__ __launch_bounds__(kBlock, ext_min_waves(SM, LOBJ, PART)) void k_wfs_e
             constexpr bool kT = SM == kSmSpheres;
             int bp = -1;
             bool walk = true;
-            // The pixel's candidate list in place of the walk: the pixel's record (16 B, a wave reads its two pixels'),
-            // then the walk's own leaf test on each entry in list order. Closest hit among spheres does not depend on
-            // the order except where two spheres share the best t exactly, which the walk
-            // resolves by its order: such a lane walks, as do the lanes of an overflow pixel (more than kCandMax
-            // candidates) and every lane of a launch without records. Scenes with lists have no moving sphere.
+            // The pixel's candidate list in place of the walk (cand_list_hit): the pixel's record (16 B, a wave reads
+            // its two pixels'). The lanes of an overflow pixel walk, those that met a tie, and every lane of a launch
+            // without records.
             if constexpr (kCand) {
                 if (I.cand) {
                     const i4v rv = gld<i4v>(I.cand, pl * 16u);
-                    uint4 rec = make_uint4((uint32_t)rv.x, (uint32_t)rv.y, (uint32_t)rv.z, (uint32_t)rv.w);
-                    if ((rec.x & 0xFFFFu) != kCandOverflow) {
-                        const RayC rc = ray_consts(r);
-                        double best = RS_INF, be = RS_INF;
-                        bool tie = false;
-                        TravStat st;
-                        // one copy of the leaf test; the record is shifted down an entry per pass (empty ones come in)
-                        for (uint32_t k = 0; k < kCandMax; ++k) {
-                            const uint32_t e = rec.x & 0xFFFFu;
-                            if (e == kCandEmpty) break;
-                            rec.x = (rec.x >> 16) | (rec.y << 16); rec.y = (rec.y >> 16) | (rec.z << 16);
-                            rec.z = (rec.z >> 16) | (rec.w << 16); rec.w = (rec.w >> 16) | 0xFFFF0000u;
-                            st.leaf();
-                            test_sphere_leaf<true>(S, ld_sphere_s(S.lsphs, (int)e), (int)e, r, rc, 0.0001, best, be, bp, &tie);
-                        }
-                        if (!tie) {
-                            walk = false;
-                            st.store();
-                            bend = best;  // kT: the winner's t
-                            if (bp >= 0 && S.lprim) bp = S.lprim[bp];
-                        }
+                    walk = !cand_list_hit(S, make_uint4((uint32_t)rv.x, (uint32_t)rv.y, (uint32_t)rv.z, (uint32_t)rv.w), r, bp, bend);
+                }
+            }
+            // A light-sample ray (the front run) of a scene with cell records: the list of the cell its origin lies in,
+            // if the ray is of the family the lists are built for (rs_light_cand.h light_member: it passes through the
+            // light's ball, ahead of its origin -- whatever produced it; every NaN fails). Origins outside the grid,
+            // other rays, overflow cells and ties walk.
+            if constexpr (kLCand) {
+                if (j < nf && S.lcand) {
+                    const double o[3] = {r.o.x, r.o.y, r.o.z}, d[3] = {r.d.x, r.d.y, r.d.z};
+                    const uint32_t cell = light_cell(S.lgrid, o);
+                    if (cell != kLightOutside && light_member(S.lgrid, o, d)) {
+                        const i4v rv = gld<i4v>(S.lcand, cell * 16u);
+                        walk = !cand_list_hit(S, make_uint4((uint32_t)rv.x, (uint32_t)rv.y, (uint32_t)rv.z, (uint32_t)rv.w), r, bp, bend);
                     }
                 }
+#ifdef RS_TRAV_STATS
+                if (j < nf) {  // front-run rays that took a list, the entries they tested, waves with a walking lane
+                    if (!walk) { atomicAdd(&g_trav_stats[1][24], 1ull); atomicAdd(&g_trav_stats[1][25], (unsigned long long)s_st_leaves[threadIdx.x]); }
+                    const unsigned long long wm = __ballot(walk);
+                    if (wm && (threadIdx.x & 63) == (unsigned)(__ffsll((long long)__ballot(1)) - 1)) atomicAdd(&g_trav_stats[1][26], 1ull);
+                }
+#endif
             }
             if (walk) bp = traverse<SM, StkT<OVF, stack_lds(SM)>, LOBJ, kT, kTop>(S, r, 0.0001, bend, stk);
             V3 add;
@@ -2616,6 +2644,47 @@ hipError_t launch_features(const SceneRef& s, const DCamera& c, const PathParams
 #endif  // the feature unit or the marcher unit
 
 #if !defined(RS_TU) || RS_TU == 1
+// The candidates of a beam: the 4-wide tree walked with the beam against each child box's bounding sphere, the sphere
+// of every leaf reached tested with the same criterion (k_cam_cand_build's comment; more than kCandMax candidates, a
+// push beyond kCandStack or no beam: overflow).
+__device__ __forceinline__ void cand_beam_walk(const DScene& S, const CandBeam& b, CandList& l) {
+    cand_list_init(l);
+    if (!b.ok || S.root4 < 0) {
+        l.n = kCandMax + 1;  // no beam: the rays walk
+        return;
+    }
+    int stk[kCandStack];
+    int sp = 0, node = S.root4;
+    while (node >= 0 && !cand_list_overflow(l)) {
+        const DNode4& N = S.nodes4[node];
+        int next = -1;
+        for (int k = 0; k < 4; ++k) {
+            const int c = N.child[k];
+            if (c == INT32_MIN) continue;
+            // the box's bounding sphere, the half diagonal rounded up
+            const double lo[3] = {(double)N.lo_x[k], (double)N.lo_y[k], (double)N.lo_z[k]};
+            const double hi[3] = {(double)N.hi_x[k], (double)N.hi_y[k], (double)N.hi_z[k]};
+            const double ctr[3] = {0.5 * (lo[0] + hi[0]), 0.5 * (lo[1] + hi[1]), 0.5 * (lo[2] + hi[2])};
+            const double ex = hi[0] - lo[0], ey = hi[1] - lo[1], ez = hi[2] - lo[2];
+            const double rad = 0.5 * sqrt(ex * ex + ey * ey + ez * ez) * (1.0 + 0x1p-40);
+            if (!cand_sphere(b, ctr, rad)) continue;
+            if (c < 0) {
+                const DSphere sp_ = ld_sphere_s(S.lsphs, ~c);
+                double along;
+                if (cand_sphere(b, sp_.c, sp_.r, &along)) cand_list_add(l, (uint32_t)~c, along);
+            } else if (next < 0) {
+                next = c;
+            } else if (sp < kCandStack) {
+                stk[sp++] = c;
+            } else {
+                l.n = kCandMax + 1;
+            }
+        }
+        if (next < 0 && sp > 0) next = stk[--sp];
+        node = next;
+    }
+}
+
 // The candidate records of the spheres mode's camera launch (rs_cam_cand.h; cam_cand in rs_internal.h): one thread
 // per lattice pixel walks the 4-wide tree with the pixel's beam against each child box's bounding sphere, tests the
 // sphere of every leaf it reaches with the same criterion and writes the pixel's 16-byte record, nearest first along
@@ -2632,44 +2701,31 @@ __global__ __launch_bounds__(kBlock) void k_cam_cand_build(const DScene* __restr
     const CandCam cc = cand_camera(C.origin, C.lb, C.hf, C.vf, C.hu, C.vu, C.aperture, P.width, P.height);
     const CandBeam b = cand_beam(cc, x, y);
     CandList l;
-    cand_list_init(l);
-    if (!b.ok || S.root4 < 0) {
-        l.n = kCandMax + 1;  // no beam for this pixel: its rays walk
-    } else {
-        int stk[kCandStack];
-        int sp = 0, node = S.root4;
-        while (node >= 0 && !cand_list_overflow(l)) {
-            const DNode4& N = S.nodes4[node];
-            int next = -1;
-            for (int k = 0; k < 4; ++k) {
-                const int c = N.child[k];
-                if (c == INT32_MIN) continue;
-                // the box's bounding sphere, the half diagonal rounded up
-                const double lo[3] = {(double)N.lo_x[k], (double)N.lo_y[k], (double)N.lo_z[k]};
-                const double hi[3] = {(double)N.hi_x[k], (double)N.hi_y[k], (double)N.hi_z[k]};
-                const double ctr[3] = {0.5 * (lo[0] + hi[0]), 0.5 * (lo[1] + hi[1]), 0.5 * (lo[2] + hi[2])};
-                const double ex = hi[0] - lo[0], ey = hi[1] - lo[1], ez = hi[2] - lo[2];
-                const double rad = 0.5 * sqrt(ex * ex + ey * ey + ez * ez) * (1.0 + 0x1p-40);
-                if (!cand_sphere(b, ctr, rad)) continue;
-                if (c < 0) {
-                    const DSphere sp_ = ld_sphere_s(S.lsphs, ~c);
-                    double along;
-                    if (cand_sphere(b, sp_.c, sp_.r, &along)) cand_list_add(l, (uint32_t)~c, along);
-                } else if (next < 0) {
-                    next = c;
-                } else if (sp < kCandStack) {
-                    stk[sp++] = c;
-                } else {
-                    l.n = kCandMax + 1;
-                }
-            }
-            if (next < 0 && sp > 0) next = stk[--sp];
-            node = next;
-        }
-    }
+    cand_beam_walk(S, b, l);
     uint32_t w[4];
     cand_list_pack(l, w);
     cand[pl] = make_uint4(w[0], w[1], w[2], w[3]);
+}
+
+// The candidate records of the spheres mode's light-sample rays (rs_light_cand.h; light_cand in rs_internal.h): one
+// thread per cell of the scene's grid walks the tree with the beam from the cell's ball to the light's, as above, and
+// writes the cell's record, nearest first along the cell-to-light axis. Once per scene commit.
+__global__ __launch_bounds__(kBlock) void k_light_cand_build(const DScene* __restrict__ Sp, uint4* __restrict__ cand) {
+    const DScene& S = *Sp;
+    const uint32_t cell = blockIdx.x * kBlock + threadIdx.x;
+    if (cell >= S.lgrid.cells) return;
+    CandList l;
+    cand_beam_walk(S, light_cell_beam(S.lgrid, cell), l);
+    uint32_t w[4];
+    cand_list_pack(l, w);
+    cand[cell] = make_uint4(w[0], w[1], w[2], w[3]);
+}
+
+hipError_t launch_light_cand_build(const SceneRef& s, uint4* cand, hipStream_t st) {
+    const uint32_t blocks = (s.host->lgrid.cells + kBlock - 1) / kBlock;
+    if (!blocks) return hipSuccess;
+    hipLaunchKernelGGL(k_light_cand_build, dim3(blocks), dim3(kBlock), 0, st, s.dev, cand);
+    return hipGetLastError();
 }
 
 hipError_t launch_cam_cand_build(const SceneRef& s, const DCamera& c, const PathParams& p, uint4* cand, hipStream_t st) {

@@ -5,6 +5,7 @@
 // in a few MB, so it is L2/MALL-resident during a frame; per-path state is what streams.
 #pragma once
 #include <stdint.h>
+#include "rs_light_cand.h"
 
 #define RS_MAX_NEST 4   // object nesting levels supported on the GPU (TfFacade / CSG chains)
 
@@ -216,6 +217,11 @@ struct DScene {
     int32_t lamb_only;       // 1: every prim's hits carry a Lambertian or a DiffuseLight material (shading classes
                              // 0 and 6 only): the flat scenes' shading kernel compiled for Lambertian alone
     float bg_lo[4], bg_hi[4];
+    // Spheres mode, one light, no motion: the cell grid of the light-sample rays' candidate lists (rs_light_cand.h;
+    // cells == 0: none) and its records, 16 bytes per cell as rs_cam_cand.h packs them, built once per commit by
+    // k_light_cand_build (null: the device had no room, or the scene gets none -- the rays walk the tree)
+    LightGrid lgrid;
+    const uint32_t* lcand;
 };
 
 // nodes of the spheres mode's tree top held in LDS per extend block: the root and three levels (85 nodes, 10.6 KiB;

@@ -13,6 +13,11 @@ for t in common 0 1 2 3 4 5 6; do
   /opt/rocm/bin/hipcc $F "$@" -c $R/raysnail_amd/csrc/rs_kernels.hip -o $B/k$t.o &
 done
 /opt/rocm/bin/hipcc $($M unit-flags-common | sed 's/-DRS_TU=-1//') "$@" -x hip -c $R/raysnail_amd/csrc/rs_host.cpp -o $B/h.o &
+# the frame operators' units and their host unit (scene-free: the flags only name them)
+for u in denoise denoise_var adaptive robust; do
+  /opt/rocm/bin/hipcc $($M unit-flags-$u) "$@" -c $R/raysnail_amd/csrc/rs_$u.hip -o $B/k_$u.o &
+done
+/opt/rocm/bin/hipcc $($M unit-flags-common | sed 's/-DRS_TU=-1//') "$@" -x hip -c $R/raysnail_amd/csrc/rs_frames.cpp -o $B/h_frames.o &
 wait
-/opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -o $R/raysnail_amd/lib/var_$N.so $B/k*.o $B/h.o
+/opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -o $R/raysnail_amd/lib/var_$N.so $B/k*.o $B/h.o $B/h_frames.o
 echo built var_$N.so

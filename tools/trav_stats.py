@@ -40,6 +40,9 @@ for name in names:
               # deferred walk lists a ray's leaves and tests them in a loop of its own (no passes counted)
               + (f"leaf passes/wave {witer/max(waves,1):.2f} leaf-pass lane use {leaves/(64*witer):.3f}" if witer
                  else "leaf passes n/a (deferred leaf list)"), flush=True)
+        if c == 1 and v[24]:  # the front run's cell lists (rs_light_cand.h): rays settled by a list, entries they tested
+            print(f"   lists: {100*v[24]/rays:.2f} % of the rays took a list, {v[25]/v[24]:.2f} entries tested per such ray; "
+                  f"a lane walked in {100*v[26]/max(waves,1):.2f} % of the waves", flush=True)
         hist = list(v[8:24])
         tot = max(1, sum(hist))
         print("   node steps per ray, 8-wide buckets (%):", " ".join(f"{8*b}:{100*h/tot:.1f}" for b, h in enumerate(hist)),
