@@ -474,6 +474,10 @@ public:
     // ... committed to the listed HIP devices instead (rs_scene_commit_devices; none = a host-only build, whose
     // renders throw RS_E_STATE); throws RS_E_STATE when the world is already committed
     rs_scene* device_scene(const std::vector<int>& devices);
+    // The id shot_mattes reports for a surface of this material: the handle it was exported with (the world is
+    // committed on first use, as by device_scene()); RS_NO_MATERIAL for a null reference (an object without a
+    // material). Throws Error RS_E_INVALID for a material the scene does not hold.
+    int32_t material_id(const MaterialRef& material);
     const HittableList& hittables() const { return hittables_; }
     const HittableList& lights() const { return lights_; }
 private:
@@ -481,6 +485,7 @@ private:
     Gradient background_;
     std::pair<double, double> time_range_;
     rs_scene* scene_ = nullptr;
+    std::unordered_map<const void*, int32_t> materials_;  // the committed scene's: material -> handle
 };
 
 // ------------------------------------------------------------------------------------- Camera ----
@@ -556,6 +561,10 @@ constexpr float ROBUST_OFF = -2.0f;  // shot_denoised_passes' default: pass_mome
 struct PassRobust { std::vector<Pixel> mean, var; std::vector<uint8_t> trimmed; };
 PassRobust pass_robust(const std::vector<std::vector<Pixel>>& frames, int W, int H, bool gamma = true,
                        float trim = ROBUST_AUTO);
+// rs_matte_extract over shot_mattes' layers (ids and cov: W * H * ranks each, rank-minor): the W x H matte of the ids in
+// `wanted` (1 .. 64 of them; World::material_id names a surface, RS_MATTE_ID_BACKGROUND what is behind everything).
+std::vector<float> matte_extract(const std::vector<int32_t>& ids, const std::vector<float>& cov, int W, int H, uint32_t ranks,
+                                 const std::vector<int32_t>& wanted);
 // rs_denoise_var's knobs (denoise's filter with the colour weight normalised by the local variance); the defaults are
 // the header's
 struct DenoiseVarSettings {
@@ -601,6 +610,13 @@ public:
     // mirror / glass bounces, tinted by the chain.
     struct Features { std::vector<Pixel> albedo, normal; };
     Features shot_features(World& world, const PixelController* pixel_map = nullptr, uint32_t max_specular = 0);
+    // The material-id matte layers of the photo (rs_render_mattes; no reference counterpart): per pixel the `ranks` ids
+    // covering most of its samples at the end of each sample's specular chain of at most max_specular bounces, their
+    // coverages, and the overflow byte; ids and cov are W * H * ranks, rank-minor. Settings, rows and mask as
+    // shot_features'.
+    struct Mattes { std::vector<int32_t> ids; std::vector<float> cov; std::vector<uint8_t> overflow; uint32_t ranks; };
+    Mattes shot_mattes(World& world, const PixelController* pixel_map = nullptr, uint32_t ranks = 4,
+                       uint32_t max_specular = 0);
     // The photo and its feature frames (the same seed, pass, rows and mask; shot_features' max_specular =
     // guide_specular), then denoise() with the photo's gamma. last_stats() is the beauty frame's.
     struct Denoised { std::vector<Pixel> denoised, beauty; };

@@ -193,6 +193,7 @@ typedef struct rs_render_settings {
 #define RS_KERNEL_WF_EXTEND  2  /* k_wf_extend: wavefront traversal (generic scenes) */
 #define RS_KERNEL_WFS_EXTEND 3  /* k_wfs_extend: wavefront traversal + material classification */
 #define RS_KERNEL_FEATURES   4  /* k_features: first-hit feature buffers (rs_render_features) */
+#define RS_KERNEL_MATTES     5  /* k_mattes: ranked material-id mattes (rs_render_mattes) */
 typedef struct rs_render_stats {
     uint64_t samples;    /* camera samples traced */
     uint64_t segments;   /* world.hit calls (path segments) */
@@ -420,6 +421,57 @@ int rs_render_features_specular(rs_scene* s, const rs_camera_desc* cam, const rs
 int rs_render_features_specular_device(rs_scene* s, const rs_camera_desc* cam, const rs_render_settings* st,
                                        const uint8_t* d_mask, uint32_t max_specular, float* d_out_albedo,
                                        float* d_out_normal, void* stream, rs_render_stats* stats);
+
+/* ---- material-id mattes: per pixel the `ranks` most covering material ids and their coverage (the model of
+ * Cryptomatte: Friedman, Jones 2015; no reference counterpart) ----
+ * out_ids (int32) and out_cov (f32) are W*H*ranks elements each, rank-minor: pixel p = y W + x, rank r at p*ranks + r;
+ * both must be non-NULL. out_overflow is W*H bytes and may be NULL (not written). Camera sample, ray, stream key,
+ * mask, row lattice, N = floor(sqrt(samples))^2, validation (RS_E_STATE before commit or on a host-only scene) and the
+ * split and gathering of several devices are rs_render_features' unchanged. RS_E_INVALID, checked with the other
+ * arguments before anything touches the device: ranks outside 1 .. RS_MATTE_MAX_RANKS, max_specular > 16, a NULL
+ * out_ids or out_cov.
+ *   a sample's id   the chain of rs_render_features_specular with the same max_specular (0: the first hit), the same
+ *                   rays and the same World::hit calls. A terminal hit gives its HitRecord's material as
+ *                   rs_probe_world_hit reports it in field 12: the handle the object was created with, RS_NO_MATERIAL
+ *                   where it has none. A MixedMaterial's own handle is the id (it is resolved only to decide whether
+ *                   the hit is specular, as the chain does). A camera ray that misses and a chain that escapes after
+ *                   a bounce both give RS_MATTE_ID_BACKGROUND. Every sample has exactly one id.
+ *   counting        c(id) = the number of the pixel's N samples with that id. A pixel with more than
+ *                   RS_MATTE_MAX_DISTINCT distinct ids keeps the RS_MATTE_MAX_DISTINCT smallest ids (signed compare),
+ *                   each with its full count, and has overflow[p] = 1; otherwise overflow[p] = 0. Nothing depends on
+ *                   the order of the samples.
+ *   ranking         the kept ids sorted by c descending, on equal c by id ascending (signed). Rank r < ranks that
+ *                   exists: ids = id, cov = (float)((double)c / (double)N). Ranks beyond the kept ids:
+ *                   (RS_MATTE_ID_EMPTY, +0.0f).
+ * Masked pixels and N == 0: every rank (RS_MATTE_ID_EMPTY, +0.0f), overflow 0. Rows off the row lattice are not written.
+ * st->depth, gamma and mode are ignored (mode must still be a valid RS_MODE_*). stats: samples, segments (the
+ * World::hit calls, as rs_render_features_specular counts them), the kernel's launches and device time, kernel_id
+ * RS_KERNEL_MATTES. Additive extension of ABI 6. */
+#define RS_MATTE_MAX_RANKS     8
+#define RS_MATTE_MAX_DISTINCT  64
+#define RS_MATTE_ID_BACKGROUND ((int32_t)-2)
+#define RS_MATTE_ID_EMPTY      ((int32_t)0x80000000)
+int rs_render_mattes(rs_scene* s, const rs_camera_desc* cam, const rs_render_settings* st, const uint8_t* mask,
+                     uint32_t ranks, uint32_t max_specular, int32_t* out_ids, float* out_cov, uint8_t* out_overflow,
+                     rs_render_stats* stats);
+/* the same into device arrays; pointers, stream and stats semantics as rs_render_features_device */
+int rs_render_mattes_device(rs_scene* s, const rs_camera_desc* cam, const rs_render_settings* st, const uint8_t* d_mask,
+                            uint32_t ranks, uint32_t max_specular, int32_t* d_out_ids, float* d_out_cov,
+                            uint8_t* d_out_overflow, void* stream, rs_render_stats* stats);
+
+/* The matte of a set of ids from rs_render_mattes' layers. Scene-free, like rs_denoise. out is W*H f32:
+ *   out[p] = the f32 sum, from +0.0f, in rank order r = 0 .. ranks-1, of cov[p*ranks + r] over the ranks whose id is
+ *   one of wanted[0 .. n_wanted) and is not RS_MATTE_ID_EMPTY; each addition rounded once.
+ * RS_E_INVALID before anything touches the device: a NULL pointer, ranks outside 1 .. RS_MATTE_MAX_RANKS, n_wanted
+ * outside 1 .. 64, W H = 0 or > 0x7FFFFFFF. wanted is a HOST array in both forms (it travels in the kernel's argument
+ * block, like rs_pass_moments_device's frame pointers).
+ * rs_matte_extract_device: one launch on `stream` of the current device, never synchronises, allocates nothing; d_out
+ * may not overlap the inputs. rs_matte_extract: host buffers; uploads, runs the device variant on the default stream,
+ * synchronises, downloads. Additive extension of ABI 6. */
+int rs_matte_extract_device(const int32_t* d_ids, const float* d_cov, uint32_t width, uint32_t height, uint32_t ranks,
+                            const int32_t* wanted, uint32_t n_wanted, float* d_out, void* stream);
+int rs_matte_extract(const int32_t* ids, const float* cov, uint32_t width, uint32_t height, uint32_t ranks,
+                     const int32_t* wanted, uint32_t n_wanted, float* out);
 
 /* ---- progressive passes (the CLI's pass loop, src/bin/raysnail.rs:311-427) ----
  * Device-resident frames (RGBA f32, W*H*4), all work on the caller's stream (NULL = default). */

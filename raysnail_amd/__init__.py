@@ -10,7 +10,8 @@ from .api import (AARect, AARectMetrics, Box, Camera, CameraBuilder, Checker, Co
                   DenoiseSettings, DenoiseVarSettings, Dielectric, Difference, DiffuseLight, DiffuseMetal, Glass, Gradient, HittableList, Intersection,
                   Lambertian, MixedMaterial, Metal, PainterController, PainterTarget, PixelController, Point3,
                   Quadric, RaysnailError, Sphere, TakePhotoSettings, TfFacade, Transform, TransformStack,
-                  TriangleMesh, Vec3, World, denoise, denoise_device, denoise_var, denoise_var_device, pass_moments,
+                  TriangleMesh, Vec3, World, denoise, denoise_device, denoise_var, denoise_var_device, matte_extract,
+                  matte_extract_device, pass_moments,
                   pass_moments_device, pass_robust, pass_robust_device, realize)
 
 __all__ = [n for n in dir() if not n.startswith("_")]

@@ -62,6 +62,12 @@ RS_DENOISE_VAR_LEVELS = 5
 RS_DENOISE_VAR_K_COLOR = 2.5
 RS_DENOISE_VAR_EPS = 1e-6
 RS_ROBUST_TRIM_AUTO = -1.0
+# rs_render_mattes' (RS_MATTE_*, RS_KERNEL_MATTES)
+RS_MATTE_MAX_RANKS = 8
+RS_MATTE_MAX_DISTINCT = 64
+RS_MATTE_ID_BACKGROUND = -2
+RS_MATTE_ID_EMPTY = -0x80000000
+RS_KERNEL_MATTES = 5
 # the adaptive pass loop's (include/raysnail_adaptive.h RS_ADAPTIVE_*)
 RS_ADAPTIVE_MIN_PASSES = 2
 RS_ADAPTIVE_MAX_PASSES = 32
@@ -271,6 +277,16 @@ def load() -> C.CDLL:
     lib.rs_render_features_specular_device.argtypes = [VP, C.POINTER(rs_camera_desc), C.POINTER(rs_render_settings), VP,
                                                        C.c_uint32, VP, VP, VP, C.POINTER(rs_render_stats)]
     lib.rs_render_features_specular_device.restype = C.c_int
+    lib.rs_render_mattes.argtypes = [VP, C.POINTER(rs_camera_desc), C.POINTER(rs_render_settings), VP, C.c_uint32,
+                                     C.c_uint32, VP, VP, VP, C.POINTER(rs_render_stats)]
+    lib.rs_render_mattes.restype = C.c_int
+    lib.rs_render_mattes_device.argtypes = [VP, C.POINTER(rs_camera_desc), C.POINTER(rs_render_settings), VP, C.c_uint32,
+                                            C.c_uint32, VP, VP, VP, VP, C.POINTER(rs_render_stats)]
+    lib.rs_render_mattes_device.restype = C.c_int
+    lib.rs_matte_extract_device.argtypes = [VP, VP, C.c_uint32, C.c_uint32, C.c_uint32, I32P, C.c_uint32, VP, VP]
+    lib.rs_matte_extract_device.restype = C.c_int
+    lib.rs_matte_extract.argtypes = [VP, VP, C.c_uint32, C.c_uint32, C.c_uint32, I32P, C.c_uint32, VP]
+    lib.rs_matte_extract.restype = C.c_int
     lib.rs_probe_world_hit.argtypes = [VP, VP, C.c_uint32, C.c_double, C.c_double, VP]
     lib.rs_scene_get_info.argtypes = [VP, C.POINTER(rs_scene_info)]
     lib.rs_scene_commit_devices.argtypes = [VP, C.POINTER(C.c_int), C.c_int]
@@ -296,7 +312,8 @@ EXPORTED_SYMBOLS = [
     "rs_scene_destroy", "rs_perlin", "rs_image", "rs_material", "rs_sphere", "rs_aarect", "rs_box", "rs_quadric", "rs_raymarcher", "rs_triangles", "rs_intersection",
     "rs_difference", "rs_transformed", "rs_constant_medium", "rs_world_add", "rs_lights_add", "rs_set_background", "rs_set_time_range",
     "rs_scene_commit", "rs_scene_commit_devices", "rs_scene_get_info", "rs_scene_set_lanes",
-    "rs_scene_set_frames_in_flight", "rs_scene_set_workspace", "rs_render", "rs_render_rows", "rs_render_device", "rs_render_device_passes", "rs_render_features", "rs_render_features_device", "rs_render_features_specular", "rs_render_features_specular_device", "rs_combine_pixels_device", "rs_noise_map_device", "rs_noise_map",
+    "rs_scene_set_frames_in_flight", "rs_scene_set_workspace", "rs_render", "rs_render_rows", "rs_render_device", "rs_render_device_passes", "rs_render_features", "rs_render_features_device", "rs_render_features_specular", "rs_render_features_specular_device",
+    "rs_render_mattes", "rs_render_mattes_device", "rs_matte_extract_device", "rs_matte_extract", "rs_combine_pixels_device", "rs_noise_map_device", "rs_noise_map",
     "rs_denoise_device", "rs_denoise",
     "rs_pass_moments_device", "rs_pass_moments", "rs_pass_robust_device", "rs_pass_robust",
     "rs_denoise_var_device", "rs_denoise_var",

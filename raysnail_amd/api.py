@@ -380,9 +380,12 @@ def _check(lib, code: int, prefix: str):
         raise RaysnailError(code, err.decode() if isinstance(err, bytes) else str(err))
 
 
-def realize(world: World, lib, handle, prefix: str = "rs_") -> None:
-    """Replay the world description into a backend scene (libraysnail_hip or the test oracle)."""
+def realize(world: World, lib, handle, prefix: str = "rs_") -> dict:
+    """Replay the world description into a backend scene (libraysnail_hip or the test oracle). Returns the handle each
+    material was created with: {id(material): (material, handle)} (the material is kept so that its id() stays its
+    own)."""
     mat_ids = {}
+    mat_objs = {}
     obj_ids = {}
     tex_ids = {}
 
@@ -443,6 +446,7 @@ def realize(world: World, lib, handle, prefix: str = "rs_") -> None:
         out = C.c_int32()
         call("material", C.byref(d), C.byref(out))
         mat_ids[id(m)] = out.value
+        mat_objs[id(m)] = (m, out.value)
         return out.value
 
     def single(h):
@@ -524,6 +528,7 @@ def realize(world: World, lib, handle, prefix: str = "rs_") -> None:
     call("set_time_range", world.time_range[0], world.time_range[1])
     add_list(world.hittables, "world_add")
     add_list(world.lights, "lights_add")
+    return mat_objs
 
 
 class DeviceScene:
@@ -536,7 +541,7 @@ class DeviceScene:
         h = C.c_void_p()
         _check(self.lib, self.lib.rs_scene_create(C.byref(h)), "rs_")
         self.handle = h
-        realize(world, self.lib, h, "rs_")
+        self._materials = realize(world, self.lib, h, "rs_")
         if devices is None:
             _check(self.lib, self.lib.rs_scene_commit(h), "rs_")
         else:
@@ -677,6 +682,56 @@ class DeviceScene:
             rc = self.lib.rs_render_features_specular_device(self.handle, C.byref(cam), C.byref(st), d_mask_ptr or None,
                                                              max_specular, *tail)
         _check(self.lib, rc, "rs_")
+        return out
+
+    def material_id(self, material: Optional[Material]) -> int:
+        """The id render_mattes reports for a surface of this material: the handle realize() created it with;
+        RS_NO_MATERIAL for None (an object without a material). Raises KeyError for a material the scene does not
+        hold. (The materials a ConstantMedium makes for itself have no Python object to ask with.)"""
+        if material is None:
+            return A.RS_NO_MATERIAL
+        ent = getattr(self, "_materials", {}).get(id(material))
+        if ent is None or ent[0] is not material:
+            raise KeyError(f"{type(material).__name__} is not a material of this scene")
+        return ent[1]
+
+    def render_mattes(self, cam: A.rs_camera_desc, st: A.rs_render_settings, ranks: int = 4, max_specular: int = 0,
+                      mask: Optional[np.ndarray] = None, ids: Optional[np.ndarray] = None,
+                      cov: Optional[np.ndarray] = None, overflow: Optional[np.ndarray] = None, want_overflow: bool = True):
+        """rs_render_mattes: per pixel the `ranks` material ids covering most of its samples and their coverage, at the
+        end of each sample's chain of at most max_specular mirror / glass bounces. Returns (ids (H, W, ranks) int32, cov
+        (H, W, ranks) float32, overflow (H, W) uint8, stats); ids / cov / overflow: arrays to write into (rows off the
+        lattice keep their values); want_overflow=False: no overflow plane (None)."""
+        H, W = cam.height, cam.width
+        R = max(0, int(ranks))
+        ids = np.full((H, W, R), A.RS_MATTE_ID_EMPTY, np.int32) if ids is None else ids
+        cov = np.zeros((H, W, R), np.float32) if cov is None else cov
+        if overflow is None and want_overflow:
+            overflow = np.zeros((H, W), np.uint8)
+        for buf, shape, dt in ((ids, (H, W, R), np.int32), (cov, (H, W, R), np.float32), (overflow, (H, W), np.uint8)):
+            assert buf is None or (buf.shape == shape and buf.dtype == dt and buf.flags.c_contiguous)
+        mptr = None
+        if mask is not None:
+            mask = np.ascontiguousarray(mask, dtype=np.uint8).reshape(H * W)
+            mptr = mask.ctypes.data_as(C.c_void_p)
+        stats = A.rs_render_stats()
+        # (an empty array has no address worth passing: ranks = 0 is the library's to refuse)
+        _check(self.lib, self.lib.rs_render_mattes(self.handle, C.byref(cam), C.byref(st), mptr, ranks, max_specular,
+                                                   ids.ctypes.data_as(C.c_void_p), cov.ctypes.data_as(C.c_void_p),
+                                                   None if overflow is None else overflow.ctypes.data_as(C.c_void_p),
+                                                   C.byref(stats)), "rs_")
+        return ids, cov, overflow, stats
+
+    def render_mattes_device(self, cam: A.rs_camera_desc, st: A.rs_render_settings, d_ids_ptr: int, d_cov_ptr: int,
+                             d_overflow_ptr: int = 0, ranks: int = 4, max_specular: int = 0, stream_ptr: int = 0,
+                             d_mask_ptr: int = 0, stats: bool = True):
+        """rs_render_mattes_device: the matte layers into device memory (d_overflow_ptr may be 0). stats as
+        render_device."""
+        out = A.rs_render_stats() if stats else None
+        _check(self.lib, self.lib.rs_render_mattes_device(self.handle, C.byref(cam), C.byref(st), d_mask_ptr or None, ranks,
+                                                          max_specular, d_ids_ptr or None, d_cov_ptr or None,
+                                                          d_overflow_ptr or None, stream_ptr or None,
+                                                          C.byref(out) if stats else None), "rs_")
         return out
 
     def render_adaptive_device(self, cam: A.rs_camera_desc, st: A.rs_render_settings, settings: "AdaptiveSettings",
@@ -843,6 +898,39 @@ def pass_robust_device(d_frame_ptrs: Sequence[int], width: int, height: int, d_m
     ptrs = _ptr_array(d_frame_ptrs)
     _check(lib, lib.rs_pass_robust_device(ptrs, n, width, height, int(bool(gamma)), t, d_mean_ptr or None,
                                           d_var_ptr or None, d_trimmed_ptr or None, stream_ptr or None), "rs_")
+
+
+def _wanted(wanted) -> np.ndarray:
+    w = np.ascontiguousarray(np.atleast_1d(np.asarray(wanted, dtype=np.int64)).reshape(-1))
+    if w.size and (w.min() < -0x80000000 or w.max() > 0x7FFFFFFF):
+        raise RaysnailError(A.RS_E_INVALID, "matte_extract: an id outside int32")
+    return w.astype(np.int32)
+
+
+def matte_extract(ids: np.ndarray, cov: np.ndarray, wanted: Sequence[int]) -> np.ndarray:
+    """rs_matte_extract on render_mattes' layers (ids (H, W, R) int32, cov (H, W, R) float32): the (H, W) float32 matte
+    of the ids in `wanted` (1 .. 64 of them; DeviceScene.material_id names a surface, RS_MATTE_ID_BACKGROUND what is
+    behind everything) -- per pixel the sum of the coverages of the ranks holding one of them."""
+    lib = A.load()
+    ids = np.ascontiguousarray(ids, dtype=np.int32)
+    cov = np.ascontiguousarray(cov, dtype=np.float32)
+    assert ids.ndim == 3 and cov.shape == ids.shape
+    H, W, R = ids.shape
+    w = _wanted(wanted)
+    out = np.empty((H, W), np.float32)
+    _check(lib, lib.rs_matte_extract(ids.ctypes.data, cov.ctypes.data, W, H, R, w.ctypes.data_as(A.I32P), w.size,
+                                     out.ctypes.data), "rs_")
+    return out
+
+
+def matte_extract_device(d_ids_ptr: int, d_cov_ptr: int, width: int, height: int, ranks: int, wanted: Sequence[int],
+                         d_out_ptr: int, stream_ptr: int = 0) -> None:
+    """rs_matte_extract_device on device layers: one launch enqueued on the stream, no synchronisation, no allocation.
+    wanted is a host sequence; d_out_ptr (width * height floats) may not overlap the layers."""
+    lib = A.load()
+    w = _wanted(wanted)
+    _check(lib, lib.rs_matte_extract_device(d_ids_ptr or None, d_cov_ptr or None, width, height, ranks,
+                                            w.ctypes.data_as(A.I32P), w.size, d_out_ptr or None, stream_ptr or None), "rs_")
 
 
 @dataclass
@@ -1113,6 +1201,21 @@ class TakePhotoSettings:
         albedo, normal, self.last_stats = world.device_scene().render_features(cam, self.settings(), mask,
                                                                                max_specular=max_specular)
         return albedo, normal
+
+    def shot_mattes(self, world: World, pixel_map: Optional[PixelController] = None, ranks: int = 4,
+                    max_specular: int = 0) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+        """The material-id matte layers of the photo (no reference counterpart): (ids (H, W, ranks) int32, cov (H, W,
+        ranks) float32, overflow (H, W) uint8) with the settings' samples, seed, pass and rows and pixel_map as the
+        mask (DeviceScene.render_mattes). world.device_scene().material_id(m) names a surface; matte_extract(ids, cov,
+        [..]) is its matte."""
+        cam = self.camera.desc
+        mask = None
+        if pixel_map is not None and type(pixel_map) is not PixelController:
+            mask = np.array([[1 if pixel_map.calculate_pixel(x, y) else 0 for x in range(cam.width)]
+                             for y in range(cam.height)], dtype=np.uint8)
+        ids, cov, overflow, self.last_stats = world.device_scene().render_mattes(cam, self.settings(), ranks, max_specular,
+                                                                                 mask)
+        return ids, cov, overflow
 
     def shot_denoised(self, world: World, pixel_map: Optional[PixelController] = None,
                       settings: Optional[DenoiseSettings] = None,

@@ -1,5 +1,5 @@
 // rs_frame_dev.h — what the kernels of the frame operators share (rs_denoise.hip, rs_denoise_var.hip, rs_adaptive.hip,
-// rs_robust.hip): pixel tests and arithmetic, the frame list in the argument block, the mean / variance stores, and the
+// rs_robust.hip, rs_matte.hip): pixel tests and arithmetic, the frame list in the argument block, the mean / variance stores, and the
 // tap geometry, weight and launch of the two a-trous kernels. All f32, every operation rounded once; nothing of the
 // scene (no rs_device.h). Everything here is inlined: each kernel's machine code is what it was with its own copy
 // (tools/kernel_isa.sh, profiles/frame_ops).

@@ -1,5 +1,5 @@
 // rs_frames.cpp — the C-ABI of the frame operators (include/raysnail_hip.h, raysnail_adaptive.h): the pass combine, the
-// noise map, the two denoisers, the pass moments and their robust form, the running moments and the sample mask. None
+// noise map, the two denoisers, the pass moments and their robust form, the running moments and the sample mask, the matte of a set of ids. None
 // of them touches an rs_scene. Each operator is a checked core (<name>_device: argument checks, then the launches of
 // rs_internal.h), its `_device` entry (run around the core) and, where the ABI has one, a host entry that stages the
 // caller's arrays in one device allocation, calls the core on the null stream and copies the results back. Argument
@@ -156,6 +156,21 @@ void pass_robust_device(const float* const* d_frames, uint32_t n_frames, uint32_
     HIP_OK(launch_pass_robust(d_frames, n_frames, width * height, gamma, trim, d_mean, d_var, d_trimmed, st));
 }
 
+// (wanted is a host array in both entries: the checks may read it)
+void validate_matte_extract(const int32_t* ids, const float* cov, uint32_t width, uint32_t height, uint32_t ranks,
+                            const int32_t* wanted, uint32_t n_wanted, const float* out) {
+    if (ranks < 1 || ranks > RS_MATTE_MAX_RANKS) throw Error(RS_E_INVALID, "matte_extract: ranks outside 1 .. 8");
+    static_assert(RS_MATTE_MAX_RANKS == 8 && kMaxWanted == 64, "the messages here");
+    if (n_wanted < 1 || n_wanted > (uint32_t)kMaxWanted) throw Error(RS_E_INVALID, "matte_extract: n_wanted outside 1 .. 64");
+    validate_frame_size(width, height, "matte_extract");
+    if (!ids || !cov || !wanted || !out) throw Error(RS_E_INVALID, "matte_extract: null argument");
+}
+void matte_extract_device(const int32_t* d_ids, const float* d_cov, uint32_t width, uint32_t height, uint32_t ranks,
+                          const int32_t* wanted, uint32_t n_wanted, float* d_out, hipStream_t st) {
+    validate_matte_extract(d_ids, d_cov, width, height, ranks, wanted, n_wanted, d_out);
+    HIP_OK(launch_matte_extract(d_ids, d_cov, width * height, ranks, wanted, n_wanted, d_out, st));
+}
+
 }  // namespace
 
 void rs::adaptive_mask_stats(const float* d_acc, const float* d_m2, const uint8_t* d_base, uint32_t width, uint32_t height,
@@ -298,6 +313,29 @@ int rs_denoise_var(const float* beauty, const float* var, const float* albedo, c
         s.sync();
         s.download(out, d_beauty);
         s.download(out_var, d_var);
+    });
+}
+
+int rs_matte_extract_device(const int32_t* d_ids, const float* d_cov, uint32_t width, uint32_t height, uint32_t ranks,
+                            const int32_t* wanted, uint32_t n_wanted, float* d_out, void* stream) {
+    return run([&] { matte_extract_device(d_ids, d_cov, width, height, ranks, wanted, n_wanted, d_out, (hipStream_t)stream); });
+}
+
+int rs_matte_extract(const int32_t* ids, const float* cov, uint32_t width, uint32_t height, uint32_t ranks,
+                     const int32_t* wanted, uint32_t n_wanted, float* out) {
+    return run([&] {
+        validate_matte_extract(ids, cov, width, height, ranks, wanted, n_wanted, out);
+        const size_t n_pix = (size_t)width * height, layer = n_pix * ranks * 4;  // the ids, the coverages, the matte
+        StreamMem m(2 * layer + n_pix * sizeof(float), nullptr);
+        char* const base = static_cast<char*>(m.mem.get());
+        int32_t* const d_ids = reinterpret_cast<int32_t*>(base);
+        float* const d_cov = reinterpret_cast<float*>(base + layer);
+        float* const d_out = reinterpret_cast<float*>(base + 2 * layer);
+        HIP_OK(hipMemcpy(d_ids, ids, layer, hipMemcpyHostToDevice));
+        HIP_OK(hipMemcpy(d_cov, cov, layer, hipMemcpyHostToDevice));
+        matte_extract_device(d_ids, d_cov, width, height, ranks, wanted, n_wanted, d_out, m.stream);
+        HIP_OK(hipStreamSynchronize(m.stream));
+        HIP_OK(hipMemcpy(out, d_out, n_pix * sizeof(float), hipMemcpyDeviceToHost));
     });
 }
 

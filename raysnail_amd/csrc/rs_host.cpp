@@ -2777,6 +2777,157 @@ void render_features(rs_scene* s, const rs_camera_desc* cam, const rs_render_set
     report_stats(s, acc, t0, stats);
 }
 
+// rs_render_mattes (host = true) and rs_render_mattes_device: render_features' split, slots, streams, events and
+// statistics with one k_mattes launch per replica and three arrays in place of the two frames -- `ranks` int32 ids and
+// `ranks` f32 coverages per pixel, and a byte of overflow (out_ovf may be null: not written, not copied). A replica
+// that does not write in place stages all three in its slot's feature buffer (ids, then coverages, then the bytes).
+void render_mattes(rs_scene* s, const rs_camera_desc* cam, const rs_render_settings* st, const uint8_t* mask, uint32_t ranks,
+                   uint32_t max_specular, int32_t* out_ids, float* out_cov, uint8_t* out_ovf, hipStream_t stream, bool host,
+                   rs_render_stats* stats) {
+    if (!out_ids || !out_cov) throw Error(RS_E_INVALID, "null argument: the matte ids or coverages");
+    if (ranks < 1 || ranks > RS_MATTE_MAX_RANKS) throw Error(RS_E_INVALID, "ranks must be 1 .. 8");
+    static_assert(RS_MATTE_MAX_RANKS == 8, "the message above");
+    if (max_specular > 16) throw Error(RS_E_INVALID, "max_specular must be at most 16");
+    validate_render(s, cam, st);
+    rs_render_stats acc{};
+    const auto t0 = std::chrono::steady_clock::now();
+    const uint32_t n = (uint32_t)s->reps.size();
+    const uint32_t W = cam->width;
+    const size_t npx = (size_t)W * cam->height;
+    const uint32_t sq = (uint32_t)std::floor(std::sqrt((double)st->samples));  // painter.rs:110-118
+    struct Part {
+        hipStream_t S = nullptr;
+        RowSet rows;
+        DeviceMem cnt;
+        Event e0, e1;
+    };
+    std::vector<Part> P(n);
+    std::vector<Event> done(n);
+    Event entry;  // what the caller queued on `stream` before this call (mask fill, use of the arrays)
+    auto timed_event = [](Event& e, hipStream_t S) {
+        hipEvent_t h;
+        HIP_OK(hipEventCreate(&h));
+        e.reset(h);
+        HIP_OK(hipEventRecord(h, S));
+    };
+    try {
+        if (!host && n > 1) {
+            DeviceGuard g(s->reps[0]->device);
+            record(entry, stream);
+        }
+        for (uint32_t k = 0; k < n; ++k) {
+            Replica& R = *s->reps[k];
+            Part& p = P[k];
+            p.rows = replica_rows(cam, st, k, n);
+            if (p.rows.count() == 0) continue;
+            DeviceGuard g(R.device);
+            const bool direct = !host && k == 0;
+            p.S = direct ? stream : R.stream;
+            if (!host && k > 0) HIP_OK(hipStreamWaitEvent(p.S, entry.get(), 0));
+            Slot* L = nullptr;
+            if (!direct || s->stack_need > kStackMax) {
+                const uint32_t n_slots = frame_slots(s);
+                L = &R.slots[R.next_slot % n_slots];
+                R.next_slot = (R.next_slot + 1) % n_slots;
+                if (!L->free_ev) HIP_OK(hipEventCreateWithFlags(&L->free_ev, hipEventDisableTiming));
+                if (L->free_rec) HIP_OK(hipStreamWaitEvent(p.S, L->free_ev, 0));
+            }
+            const uint8_t* d_mask = mask;
+            int32_t* d_i = out_ids;
+            float* d_c = out_cov;
+            uint8_t* d_o = out_ovf;
+            if (!direct) {
+                ensure(*L, L->d_feat, L->feat_cap, npx * 2 * ranks + (npx + 3) / 4);
+                d_i = reinterpret_cast<int32_t*>(L->d_feat);
+                d_c = L->d_feat + npx * ranks;
+                d_o = out_ovf ? reinterpret_cast<uint8_t*>(L->d_feat + npx * 2 * ranks) : nullptr;
+                if (mask) {
+                    ensure(*L, L->d_mask, L->mask_cap, npx);
+                    HIP_OK(hipMemcpyAsync(L->d_mask, mask, npx, host ? hipMemcpyHostToDevice : hipMemcpyDefault, p.S));
+                    d_mask = L->d_mask;
+                }
+            }
+            PathParams pp{};
+            pp.n_pix_local = (uint32_t)((uint64_t)p.rows.count() * W);
+            pp.width = W; pp.height = cam->height; pp.row_begin = p.rows.begin; pp.row_step = p.rows.step;
+            pp.sqrt_spp = sq;
+            pp.key_base = splitmix64_h(splitmix64_h(st->seed) ^ (uint64_t)st->pass);
+            pp.mask = d_mask;
+            // the grid bound of the beauty frame's launches (render_enqueue), so the overflow array is sized once
+            const uint32_t wide = (uint32_t)std::max(1, R.n_cu * 64);
+            const uint32_t grid = std::max(std::max((uint32_t)std::max(1, R.n_cu * std::max(1, R.ext_bpc)),
+                                                    (uint32_t)std::max(1, R.n_cu * std::max(1, R.shade_bpc))), wide);
+            ensure_stack_overflow(s, R, (uint64_t)grid * kBlock);
+            const SceneRef ds = R.ref();
+            if (stats) {
+                void* c = nullptr;
+                HIP_OK(hipMalloc(&c, sizeof(unsigned long long)));
+                p.cnt.reset(c);
+                HIP_OK(hipMemsetAsync(c, 0, sizeof(unsigned long long), p.S));
+                timed_event(p.e0, p.S);
+            }
+            HIP_OK(launch_mattes(ds, make_camera(*cam), pp, max_specular, ranks, d_i, d_c, d_o,
+                                 (unsigned long long*)p.cnt.get(), s->scene_mode, wide, p.S));
+            if (stats) timed_event(p.e1, p.S);
+            if (!direct) {
+                const hipMemcpyKind kind = host ? hipMemcpyDeviceToHost : hipMemcpyDefault;
+                const size_t row_bytes = (size_t)W * ranks * 4;
+                const size_t off = (size_t)p.rows.begin * W * ranks;
+                HIP_OK(hipMemcpy2DAsync(out_ids + off, row_bytes * p.rows.step, d_i + off, row_bytes * p.rows.step,
+                                        row_bytes, p.rows.count(), kind, p.S));
+                HIP_OK(hipMemcpy2DAsync(out_cov + off, row_bytes * p.rows.step, d_c + off, row_bytes * p.rows.step,
+                                        row_bytes, p.rows.count(), kind, p.S));
+                if (out_ovf) {
+                    const size_t boff = (size_t)p.rows.begin * W;
+                    HIP_OK(hipMemcpy2DAsync(out_ovf + boff, (size_t)W * p.rows.step, d_o + boff, (size_t)W * p.rows.step, W,
+                                            p.rows.count(), kind, p.S));
+                }
+                if (!host) record(done[k], p.S);
+            }
+            if (L) {
+                HIP_OK(hipEventRecord(L->free_ev, p.S));
+                L->free_rec = true;
+            }
+        }
+        if (!host) {
+            DeviceGuard g(s->reps[0]->device);
+            for (uint32_t k = 1; k < n; ++k)
+                if (done[k]) HIP_OK(hipStreamWaitEvent(stream, done[k].get(), 0));
+        }
+        if (host || stats) {  // the device call without stats returns once everything is enqueued (asynchronous)
+            for (uint32_t k = 0; k < n; ++k) {
+                Part& p = P[k];
+                if (p.rows.count() == 0) continue;
+                DeviceGuard g(s->reps[k]->device);
+                HIP_OK(hipStreamSynchronize(p.S));
+                if (!stats) continue;
+                unsigned long long segs = 0;
+                HIP_OK(hipMemcpy(&segs, p.cnt.get(), sizeof(segs), hipMemcpyDeviceToHost));
+                float ms = 0;
+                HIP_OK(hipEventElapsedTime(&ms, p.e0.get(), p.e1.get()));
+                const uint64_t pix = (uint64_t)p.rows.count() * W;
+                acc.samples += pix * sq * sq;  // masked-out pixels included (they trace nothing)
+                acc.segments += segs;
+                acc.path_ms += ms; acc.kernel_ms += ms;
+                acc.launches += 1; acc.kernel_launches += 1;
+                acc.kernel_bytes += pix * (8u * ranks + (out_ovf ? 1u : 0u) + (mask ? 1u : 0u));
+            }
+            if (!host && stats) {
+                DeviceGuard g(s->reps[0]->device);
+                HIP_OK(hipStreamSynchronize(stream));
+            }
+        }
+    } catch (...) {
+        for (uint32_t k = 0; k < n; ++k) {  // drain what was enqueued before the buffers go away
+            DeviceGuard g(s->reps[k]->device);
+            (void)hipDeviceSynchronize();
+        }
+        throw;
+    }
+    acc.kernel_id = RS_KERNEL_MATTES;
+    report_stats(s, acc, t0, stats);
+}
+
 // rs_render_rows: the frame's row lattice in bands, each band a frame of its own on the replicas'
 // frame slots (band b on replica b % n), up to frames_in_flight bands in flight per replica; each
 // band's rows are copied to pinned host memory on the replica's stream, and once a band's copy is
@@ -3213,6 +3364,23 @@ int rs_render_features_specular_device(rs_scene* s, const rs_camera_desc* cam, c
                                        float* d_out_normal, void* stream, rs_render_stats* stats) {
     return run([&] {
         render_features(S(s), cam, st, d_mask, max_specular, d_out_albedo, d_out_normal, (hipStream_t)stream, false, stats);
+    });
+}
+
+int rs_render_mattes(rs_scene* s, const rs_camera_desc* cam, const rs_render_settings* st, const uint8_t* mask,
+                     uint32_t ranks, uint32_t max_specular, int32_t* out_ids, float* out_cov, uint8_t* out_overflow,
+                     rs_render_stats* stats) {
+    return run([&] {
+        render_mattes(S(s), cam, st, mask, ranks, max_specular, out_ids, out_cov, out_overflow, nullptr, true, stats);
+    });
+}
+
+int rs_render_mattes_device(rs_scene* s, const rs_camera_desc* cam, const rs_render_settings* st, const uint8_t* d_mask,
+                            uint32_t ranks, uint32_t max_specular, int32_t* d_out_ids, float* d_out_cov,
+                            uint8_t* d_out_overflow, void* stream, rs_render_stats* stats) {
+    return run([&] {
+        render_mattes(S(s), cam, st, d_mask, ranks, max_specular, d_out_ids, d_out_cov, d_out_overflow, (hipStream_t)stream,
+                      false, stats);
     });
 }
 

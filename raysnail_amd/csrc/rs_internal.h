@@ -253,6 +253,17 @@ hipError_t launch_probe_hit(const SceneRef& s, const double* rays, uint32_t n, d
 // that many bounces (k_features_spec).
 hipError_t launch_features(const SceneRef& s, const DCamera& c, const PathParams& p, uint32_t max_specular, float* out_albedo,
                            float* out_normal, unsigned long long* seg_counter, int sm, uint32_t max_blocks, hipStream_t st);
+// Material-id mattes (k_mattes; contract in raysnail_hip.h, rs_render_mattes): the lattice pixels of p as
+// launch_features', into out_ids / out_cov (`ranks` entries per pixel of the full frame, 1 .. RS_MATTE_MAX_RANKS) and
+// out_ovf (a byte per pixel; may be null). max_specular (0 .. 16), seg_counter and max_blocks as launch_features'.
+hipError_t launch_mattes(const SceneRef& s, const DCamera& c, const PathParams& p, uint32_t max_specular, uint32_t ranks,
+                         int32_t* out_ids, float* out_cov, uint8_t* out_ovf, unsigned long long* seg_counter, int sm,
+                         uint32_t max_blocks, hipStream_t st);
+// The matte of a set of ids (rs_matte.hip; contract in raysnail_hip.h, rs_matte_extract): one k_matte_extract launch,
+// the n_wanted (1 .. kMaxWanted) ids of the host array `wanted` in the kernel's argument block.
+constexpr int kMaxWanted = 64;
+hipError_t launch_matte_extract(const int32_t* ids, const float* cov, uint32_t n_pix, uint32_t ranks, const int32_t* wanted,
+                                uint32_t n_wanted, float* out, hipStream_t st);
 // The a-trous denoiser (rs_denoise.hip; contract in raysnail_hip.h): k_dn_prepare, then `levels` k_dn_atrous launches
 // ping-ponging between the two W H float4 halves of `work`, the last one finishing into `out` (which may be `beauty`).
 // albedo / normal may be null; ic[i] is level i's colour constant; width height <= 2^31 - 1 is the caller's check.

@@ -25,7 +25,8 @@
 // mode, in parallel. RS_TU undefined: everything in one unit (tools/regs.sh, build_variant.sh);
 // RS_TU = -1: the common unit (mode-independent kernels, the launchers that dispatch on the scene
 // mode); RS_TU = k >= 0: scene mode k's launch_*_sm<k> instantiations only; RS_TU = 6: the feature
-// unit (k_features and k_features_spec with the generic World::hit; no scene mode's launchers).
+// unit (k_features and k_features_spec with the generic World::hit; no scene mode's launchers);
+// RS_TU = 7: the matte unit (k_mattes with the generic World::hit, likewise).
 // RS_TU_SUFFIX names the unit in its exported debug symbol (nothing, _c, _<k>).
 #define RS_PASTE_(a, b) a##b
 #define RS_PASTE(a, b) RS_PASTE_(a, b)
@@ -41,6 +42,10 @@
 #define RS_TU_COMMON 0
 #define RS_TU_MODES 0
 #define RS_TU_SUFFIX _6
+#elif RS_TU == 7
+#define RS_TU_COMMON 0
+#define RS_TU_MODES 0
+#define RS_TU_SUFFIX _7
 #else
 #define RS_TU_COMMON 0
 #define RS_TU_MODES 1
@@ -2642,6 +2647,274 @@ hipError_t launch_features(const SceneRef& s, const DCamera& c, const PathParams
 }
 #endif
 #endif  // the feature unit or the marcher unit
+
+#if !defined(RS_TU) || RS_TU == 5 || RS_TU == 7
+// Material-id mattes (the contract is rs_render_mattes' in raysnail_hip.h): per pixel the `ranks` ids
+// that most of its N samples end on, with their share of the samples. SM as k_features': kSmGeneric in the matte unit,
+// kSmMarch in the marcher's.
+
+// One sample's id: features_chain's rays and World::hit calls (its statements, without the tint, the depth and the
+// albedo, none of which a ray depends on), ending in the terminal hit's own material handle -- a MixedMaterial is
+// resolved only to classify the hit -- or the background id when the camera ray or a bounced ray leaves the scene.
+template <int SM>
+__device__ __forceinline__ int32_t mattes_chain(const DScene& S, Ray r, uint32_t max_specular, const Stk& stk,
+                                                uint32_t& segs) {
+    for (uint32_t k = 0;; ++k) {
+        Hit h;
+        ++segs;
+        if (!world_hit<SM>(S, r, 0.0001, h, stk)) return RS_MATTE_ID_BACKGROUND;
+        bool bounced = false;
+        if (k < max_specular) {
+            int mi = h.mat >= 0 ? h.mat : S.default_mat;
+            for (int j = 0; j < 16 && S.mats[mi].kind == RS_MAT_MIXED; ++j) mi = S.mats[mi].mix_a;
+            const DMaterial& M = S.mats[mi];
+            if (M.kind == RS_MAT_METAL) {
+                const V3 rf = reflect_v(r.d, h.n);
+                if (dot(rf, h.n) > 0.0) {
+                    r.o = h.p; r.d = rf;
+                    bounced = true;
+                }
+            } else if (M.kind == RS_MAT_DIELECTRIC) {
+                V3 nd;
+                const double cos_theta = dot(-r.d, h.n);
+                const double sin_theta = sqrt(1.0 - cos_theta * cos_theta);
+                const double refr = h.outside ? M.enter_refractive : M.outer_refractive;
+                if (!(refr * sin_theta > 1.0)) {
+                    const V3 rp = (r.d + cos_theta * h.n) * refr;
+                    const V3 rq = (-sqrt(1.0 - len2(rp))) * h.n;
+                    nd = rp + rq;
+                } else {
+                    nd = reflect_v(r.d, h.n);
+                }
+                r.o = h.p; r.d = nd;
+                bounced = true;
+            }
+        }
+        if (!bounced) return (int32_t)h.mat;
+    }
+}
+
+// A wave's share of the reduction's LDS: the chunk's sample ids by lane and which lanes hold an id's first occurrence
+// in their pixel's segment; the chunk's distinct (id, count) lists, one segment of nc entries per pixel, each sorted by
+// id; the table of a pixel of more than 64 samples (sorted by id, at most RS_MATTE_MAX_DISTINCT entries); the number of
+// entries each pixel of the group ends with.
+struct MatteLds {
+    int32_t cid[64];
+    uint32_t first[64];
+    int32_t lid[64];
+    uint32_t lcnt[64];
+    int32_t tid[RS_MATTE_MAX_DISTINCT];
+    uint32_t tcnt[RS_MATTE_MAX_DISTINCT];
+    uint32_t size[64];
+};
+static_assert(RS_MATTE_MAX_DISTINCT == 64, "a table entry per lane");
+__device__ __forceinline__ uint64_t lanes_below(uint32_t n) { return n >= 64 ? ~0ull : (1ull << n) - 1ull; }
+
+// k_features' work distribution (nc = min(N, 64) samples of each of 64 / nc consecutive lattice pixels per chunk, more
+// than 64 samples in chunks of 64 of one pixel), and in place of its f64 sums a count-and-rank of integer ids by
+// counting over LDS broadcasts: every lane reads the ids of its pixel's segment one after the other (all lanes of a
+// pixel read one address, the pixels of a group different banks), so a lane knows how often its id occurs, whether it
+// is the first lane holding it, and how many distinct ids of the segment are smaller. The first lanes write the
+// chunk's (id, count) list sorted by id. A pixel of at most 64 samples is ranked from that list. A pixel of more
+// merges each chunk's list into its table, lane i holding table entry i and list entry i: an id already in the table
+// adds its count there; the others find their place among the table's ids by counting and, among themselves, by a
+// ballot's population count below the lane (the list is sorted); a table entry moves up by the new ids below it.
+// Places from 64 on are dropped: the table keeps the smallest ids with their full counts (an id dropped once has 64
+// smaller ones before it for good). Ranks are counted the same way, by (count descending, id ascending).
+// Counts are integers: nothing depends on an order but the rule. The block's four waves step through the loop
+// together, as k_features' do; every barrier is in block-uniform control flow.
+template <int SM>
+__global__ __launch_bounds__(kBlock, SM == kSmMarch ? 1 : 2) void k_mattes(
+    const DScene* __restrict__ Sp, DCamera C, PathParams P, uint32_t max_specular, uint32_t ranks,
+    int32_t* __restrict__ out_ids, float* __restrict__ out_cov, uint8_t* __restrict__ out_ovf,
+    unsigned long long* __restrict__ seg_counter) {
+    const DScene& S = *Sp;  // the scene lives in device memory: no by-value copy in scratch
+    __shared__ int stk_all[kStackMax * kBlock];
+    __shared__ MatteLds lds_all[kBlock / 64];
+    const Stk stk = make_stk(S, stk_all);
+    const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    MatteLds& L = lds_all[wave];
+    const uint32_t N = P.sqrt_spp * P.sqrt_spp;
+    const uint32_t nc = N < 64 ? (N ? N : 1u) : 64u;  // samples of a pixel per chunk
+    const uint32_t ppw = 64 / nc;                     // pixels per wave group
+    const uint32_t n_chunks = (N + 63) / 64;
+    const uint64_t n_groups = ((uint64_t)P.n_pix_local + ppw - 1) / ppw;
+    const uint64_t n_gblocks = (n_groups + kBlock / 64 - 1) / (kBlock / 64);
+    const uint32_t lp = lane / nc, ls = lane - lp * nc;  // this lane's pixel of the group and sample of the chunk
+    const uint32_t seg = lp < ppw ? lp * nc : 0u;        // its pixel's segment (the lanes past the last pixel: idle)
+    const double sq = (double)P.sqrt_spp, hh = (double)P.height;
+    uint32_t segs = 0;
+    for (uint64_t gb = blockIdx.x; gb < n_gblocks; gb += gridDim.x) {
+        const uint64_t pl0 = (gb * (kBlock / 64) + wave) * ppw;  // the group's first lattice pixel
+        const uint64_t pl = pl0 + lp;
+        bool live = lp < ppw && pl < P.n_pix_local;
+        uint32_t x = 0, y = 0;
+        uint64_t pix = 0;
+        if (live) {
+            x = (uint32_t)(pl % P.width);
+            y = P.row_begin + (uint32_t)(pl / P.width) * P.row_step;
+            pix = (uint64_t)y * P.width + x;
+            live = !P.mask || P.mask[pix];  // painter.rs:204-210: a masked pixel traces nothing
+        }
+        uint32_t m = 0;    // distinct ids of this lane's pixel in the chunk
+        uint32_t t = 0;    // N > 64 (one pixel per wave): entries of the pixel's table
+        uint32_t ovf = 0;  // ... and whether an id was dropped from it
+        for (uint32_t ch = 0; ch < n_chunks; ++ch) {
+            const uint32_t s = ch * 64 + ls;
+            const bool valid = live && s < N;
+            int32_t my = RS_MATTE_ID_EMPTY;
+            if (valid) {
+                Rng rng;
+                rng.seed_from_u64(splitmix64(splitmix64(P.key_base ^ pix) ^ (uint64_t)s));
+                const uint32_t si = s % P.sqrt_spp, sj = s / P.sqrt_spp;
+                const double xo = (double)x + ((double)si + 0.5) / sq;
+                const double yo = (double)y + ((double)sj + 0.5) / sq;
+                const Ray r = camera_ray(C, xo / (double)P.width, (hh - 1.0 - yo) / hh, rng);  // medium key 0
+                my = mattes_chain<SM>(S, r, max_specular, stk, segs);  // (no barrier inside: lanes idle to the longest chain)
+            }
+            L.cid[lane] = my;
+            __syncthreads();
+            const uint32_t cnt = N - ch * 64 < nc ? N - ch * 64 : nc;  // samples in this chunk
+            uint32_t same = 0, before = 0;
+            for (uint32_t k = 0; k < cnt; ++k) {
+                const bool eq = L.cid[seg + k] == my;
+                same += eq ? 1u : 0u;
+                before += eq && k < ls ? 1u : 0u;
+            }
+            const bool first = valid && before == 0;
+            L.first[lane] = first ? 1u : 0u;
+            __syncthreads();
+            uint32_t pos = 0;
+            m = 0;
+            for (uint32_t k = 0; k < cnt; ++k) {
+                const uint32_t f = L.first[seg + k];
+                m += f;
+                pos += f && L.cid[seg + k] < my ? 1u : 0u;
+            }
+            if (first) {
+                L.lid[seg + pos] = my;
+                L.lcnt[seg + pos] = same;
+            }
+            __syncthreads();
+            if (n_chunks > 1) {  // one pixel per wave: seg = 0, ls = lane, m and t are the same in every lane
+                const bool ce = lane < m;
+                int32_t c = 0;
+                uint32_t cc = 0, less = 0;
+                int match = -1;
+                if (ce) {
+                    c = L.lid[lane];
+                    cc = L.lcnt[lane];
+                    for (uint32_t i = 0; i < t; ++i) {
+                        const int32_t a = L.tid[i];
+                        less += a < c ? 1u : 0u;
+                        match = a == c ? (int)i : match;
+                    }
+                    if (match >= 0) L.tcnt[match] += cc;  // (the list's ids are distinct: one lane per entry)
+                }
+                const bool is_new = ce && match < 0;
+                const uint64_t new_mask = __ballot(is_new);
+                __syncthreads();
+                int32_t a = 0;
+                uint32_t ac = 0, apos = 64;
+                if (lane < t) {
+                    a = L.tid[lane];
+                    ac = L.tcnt[lane];
+                    uint32_t cl = 0;  // the list's ids below a: a prefix of the sorted list
+                    for (uint32_t k = 0; k < m; ++k) cl += L.lid[k] < a ? 1u : 0u;
+                    apos = lane + (uint32_t)__popcll(new_mask & lanes_below(cl));
+                }
+                const uint32_t cpos = less + (uint32_t)__popcll(new_mask & lanes_below(lane));
+                __syncthreads();
+                if (apos < 64) { L.tid[apos] = a; L.tcnt[apos] = ac; }
+                if (is_new && cpos < 64) { L.tid[cpos] = c; L.tcnt[cpos] = cc; }
+                const uint32_t tn = t + (uint32_t)__popcll(new_mask);
+                ovf |= tn > 64 ? 1u : 0u;
+                t = tn < 64 ? tn : 64u;
+                __syncthreads();
+            }
+        }
+        // the pixel's entries: its table, or its segment of the one chunk's list (none without samples)
+        const int32_t* const eid = n_chunks > 1 ? L.tid : L.lid + seg;
+        const uint32_t* const ecnt = n_chunks > 1 ? L.tcnt : L.lcnt + seg;
+        const uint32_t esz = n_chunks > 1 ? t : m;
+        if (ls == 0 && lp < ppw) L.size[lp] = esz;
+        __syncthreads();
+        if (lp < ppw && ls < esz) {  // (a pixel has at least as many lanes as entries; esz > 0: the pixel is live)
+            const int32_t id = eid[ls];
+            const uint32_t c = ecnt[ls];
+            uint32_t rank = 0;
+            for (uint32_t k = 0; k < esz; ++k) {
+                const int32_t o = eid[k];
+                const uint32_t oc = ecnt[k];
+                rank += oc > c || (oc == c && o < id) ? 1u : 0u;
+            }
+            if (rank < ranks) {
+                out_ids[pix * ranks + rank] = id;
+                out_cov[pix * ranks + rank] = (float)((double)c / (double)N);
+            }
+        }
+        // the ranks past a pixel's entries (all of them in a masked pixel), and the overflow bytes
+        for (uint32_t q = lane; q < ppw * ranks; q += 64) {
+            const uint32_t p = q / ranks, r = q - p * ranks;
+            const uint64_t qpl = pl0 + p;
+            if (qpl < P.n_pix_local && r >= L.size[p]) {
+                const uint32_t qx = (uint32_t)(qpl % P.width);
+                const uint32_t qy = P.row_begin + (uint32_t)(qpl / P.width) * P.row_step;
+                const uint64_t qpix = (uint64_t)qy * P.width + qx;
+                out_ids[qpix * ranks + r] = RS_MATTE_ID_EMPTY;
+                out_cov[qpix * ranks + r] = 0.0f;
+            }
+        }
+        if (out_ovf && lane < ppw && pl0 + lane < P.n_pix_local) {
+            const uint64_t qpl = pl0 + lane;
+            const uint32_t qx = (uint32_t)(qpl % P.width);
+            const uint32_t qy = P.row_begin + (uint32_t)(qpl / P.width) * P.row_step;
+            out_ovf[(uint64_t)qy * P.width + qx] = (uint8_t)ovf;  // (several pixels per wave: no table, never set)
+        }
+        // (the next group's barriers separate these reads of the wave's LDS from its writes)
+    }
+    if (seg_counter) {  // statistics: world.hit calls, one atomic per wave
+        unsigned long long s64 = segs;
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) s64 += __shfl_xor(s64, off, 64);
+        if (lane == 0 && s64) atomicAdd(seg_counter, s64);
+    }
+}
+
+// blocks: as features_launch's
+template <int SM>
+static hipError_t mattes_launch(const SceneRef& s, const DCamera& c, const PathParams& p, uint32_t max_specular,
+                                uint32_t ranks, int32_t* out_ids, float* out_cov, uint8_t* out_ovf,
+                                unsigned long long* seg_counter, uint32_t max_blocks, hipStream_t st) {
+    const uint32_t N = p.sqrt_spp * p.sqrt_spp;
+    const uint32_t ppw = 64 / (N < 64 ? (N ? N : 1u) : 64u);
+    const uint64_t groups = ((uint64_t)p.n_pix_local + ppw - 1) / ppw;
+    const uint64_t blocks = std::min<uint64_t>((groups + kBlock / 64 - 1) / (kBlock / 64), max_blocks);
+    if (!blocks) return hipSuccess;
+    hipLaunchKernelGGL(k_mattes<SM>, dim3((uint32_t)blocks), dim3(kBlock), 0, st, s.dev, c, p, max_specular, ranks, out_ids,
+                       out_cov, out_ovf, seg_counter);
+    return hipGetLastError();
+}
+#if !defined(RS_TU) || RS_TU == 5
+hipError_t mattes_march(const SceneRef& s, const DCamera& c, const PathParams& p, uint32_t max_specular, uint32_t ranks,
+                        int32_t* out_ids, float* out_cov, uint8_t* out_ovf, unsigned long long* seg_counter,
+                        uint32_t max_blocks, hipStream_t st) {
+    return mattes_launch<kSmMarch>(s, c, p, max_specular, ranks, out_ids, out_cov, out_ovf, seg_counter, max_blocks, st);
+}
+#endif
+#if !defined(RS_TU) || RS_TU == 7
+hipError_t mattes_march(const SceneRef& s, const DCamera& c, const PathParams& p, uint32_t max_specular, uint32_t ranks,
+                        int32_t* out_ids, float* out_cov, uint8_t* out_ovf, unsigned long long* seg_counter,
+                        uint32_t max_blocks, hipStream_t st);
+hipError_t launch_mattes(const SceneRef& s, const DCamera& c, const PathParams& p, uint32_t max_specular, uint32_t ranks,
+                         int32_t* out_ids, float* out_cov, uint8_t* out_ovf, unsigned long long* seg_counter, int sm,
+                         uint32_t max_blocks, hipStream_t st) {
+    if (sm == kSmMarch)
+        return mattes_march(s, c, p, max_specular, ranks, out_ids, out_cov, out_ovf, seg_counter, max_blocks, st);
+    return mattes_launch<kSmGeneric>(s, c, p, max_specular, ranks, out_ids, out_cov, out_ovf, seg_counter, max_blocks, st);
+}
+#endif
+#endif  // the matte unit or the marcher unit
 
 #if !defined(RS_TU) || RS_TU == 1
 // The candidates of a beam: the 4-wide tree walked with the beam against each child box's bounding sphere, the sphere

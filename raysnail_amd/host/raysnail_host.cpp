@@ -280,7 +280,7 @@ World::~World() {
 
 World::World(World&& o) noexcept
     : hittables_(std::move(o.hittables_)), lights_(std::move(o.lights_)), background_(o.background_),
-      time_range_(o.time_range_), scene_(o.scene_) {
+      time_range_(o.time_range_), scene_(o.scene_), materials_(std::move(o.materials_)) {
     o.scene_ = nullptr;
 }
 
@@ -292,6 +292,7 @@ World& World::operator=(World&& o) noexcept {
         background_ = o.background_;
         time_range_ = o.time_range_;
         scene_ = o.scene_;
+        materials_ = std::move(o.materials_);
         o.scene_ = nullptr;
     }
     return *this;
@@ -309,13 +310,15 @@ void World::export_to(SceneSink& sink) const {
 }
 
 // export the world into a new scene and commit it: to the current device, or to `devices` when given
-static rs_scene* commit_world(const World& w, const std::vector<int>* devices) {
+static rs_scene* commit_world(const World& w, const std::vector<int>* devices,
+                              std::unordered_map<const void*, int32_t>& materials) {
     rs_scene* s = nullptr;
     check_rs(rs_scene_create(&s));
     try {
         SceneSink sink(hip_sink_api(), s);
         w.export_to(sink);
         check_rs(devices ? rs_scene_commit_devices(s, devices->data(), (int)devices->size()) : rs_scene_commit(s));
+        materials = std::move(sink.materials);
     } catch (...) {
         rs_scene_destroy(s);
         throw;
@@ -324,14 +327,22 @@ static rs_scene* commit_world(const World& w, const std::vector<int>* devices) {
 }
 
 rs_scene* World::device_scene() {
-    if (!scene_) scene_ = commit_world(*this, nullptr);
+    if (!scene_) scene_ = commit_world(*this, nullptr, materials_);
     return scene_;
 }
 
 rs_scene* World::device_scene(const std::vector<int>& devices) {
     if (scene_) throw Error(RS_E_STATE, "world already committed");
-    scene_ = commit_world(*this, &devices);
+    scene_ = commit_world(*this, &devices, materials_);
     return scene_;
+}
+
+int32_t World::material_id(const MaterialRef& material) {
+    if (!material) return RS_NO_MATERIAL;
+    device_scene();
+    const auto it = materials_.find(material.get());
+    if (it == materials_.end()) throw Error(RS_E_INVALID, "material_id: not a material of this world");
+    return it->second;
 }
 
 // ------------------------------------------------------------------------------------- Camera ----
@@ -393,6 +404,32 @@ TakePhotoSettings::Features TakePhotoSettings::shot_features(World& world, const
     check_rs(max_specular == 0 ? rs_render_features(world.device_scene(), &cam, &st, m, a, n, &stats_)
                                : rs_render_features_specular(world.device_scene(), &cam, &st, m, max_specular, a, n, &stats_));
     return f;
+}
+
+TakePhotoSettings::Mattes TakePhotoSettings::shot_mattes(World& world, const PixelController* pixel_map, uint32_t ranks,
+                                                         uint32_t max_specular) {
+    const rs_camera_desc& cam = camera_.desc();
+    const size_t npx = (size_t)cam.width * cam.height;
+    const std::vector<uint8_t> mask = mask_of(pixel_map);
+    const size_t r = ranks <= RS_MATTE_MAX_RANKS ? ranks : 0;  // (an invalid count is the library's to refuse)
+    Mattes m{std::vector<int32_t>(npx * r, RS_MATTE_ID_EMPTY), std::vector<float>(npx * r, 0.f),
+             std::vector<uint8_t>(npx, 0), ranks};
+    const rs_render_settings st = settings();
+    check_rs(rs_render_mattes(world.device_scene(), &cam, &st, mask.empty() ? nullptr : mask.data(), ranks, max_specular,
+                              m.ids.data(), m.cov.data(), m.overflow.data(), &stats_));
+    return m;
+}
+
+std::vector<float> matte_extract(const std::vector<int32_t>& ids, const std::vector<float>& cov, int W, int H, uint32_t ranks,
+                                 const std::vector<int32_t>& wanted) {
+    if (W < 0 || H < 0) throw Error(RS_E_INVALID, "matte_extract: negative size");
+    const size_t npx = (size_t)W * (size_t)H;
+    if (ids.size() != npx * ranks || cov.size() != npx * ranks) throw Error(RS_E_INVALID, "matte_extract: layer size mismatch");
+    if (wanted.size() > 64) throw Error(RS_E_INVALID, "matte_extract: n_wanted outside 1 .. 64");
+    std::vector<float> out(npx, 0.f);
+    check_rs(rs_matte_extract(ids.data(), cov.data(), (uint32_t)W, (uint32_t)H, ranks, wanted.data(), (uint32_t)wanted.size(),
+                              out.data()));
+    return out;
 }
 
 void denoise(std::vector<Pixel>& pixels, const std::vector<Pixel>* albedo, const std::vector<Pixel>* normal, int W, int H,

@@ -8,13 +8,13 @@ R=$(cd "$(dirname "$0")/.." && pwd)
 N=$1; shift
 B=/tmp/rs_var_$N; mkdir -p $B
 M="make -s --no-print-directory -C $R/raysnail_amd/csrc"
-for t in common 0 1 2 3 4 5 6; do
+for t in common 0 1 2 3 4 5 6 7; do
   if [ -n "${NOUNIT:-}" ] && [ $t != common ]; then F="$($M unit-flags-common | sed 's/-DRS_TU=-1//') -DRS_TU=$t"; else F=$($M unit-flags-$t); fi
   /opt/rocm/bin/hipcc $F "$@" -c $R/raysnail_amd/csrc/rs_kernels.hip -o $B/k$t.o &
 done
 /opt/rocm/bin/hipcc $($M unit-flags-common | sed 's/-DRS_TU=-1//') "$@" -x hip -c $R/raysnail_amd/csrc/rs_host.cpp -o $B/h.o &
 # the frame operators' units and their host unit (scene-free: the flags only name them)
-for u in denoise denoise_var adaptive robust; do
+for u in denoise denoise_var adaptive robust matte; do
   /opt/rocm/bin/hipcc $($M unit-flags-$u) "$@" -c $R/raysnail_amd/csrc/rs_$u.hip -o $B/k_$u.o &
 done
 /opt/rocm/bin/hipcc $($M unit-flags-common | sed 's/-DRS_TU=-1//') "$@" -x hip -c $R/raysnail_amd/csrc/rs_frames.cpp -o $B/h_frames.o &

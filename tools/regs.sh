@@ -1,6 +1,6 @@
 #!/bin/bash
 # dev: VGPRs / scratch / occupancy of the kernels of one kernel unit (a unit of rs_kernels.hip, or one of the frame
-# operators' units rs_denoise.hip, rs_denoise_var.hip, rs_adaptive.hip, rs_robust.hip: tools/unit_src.sh) whose names
+# operators' units rs_denoise.hip, rs_denoise_var.hip, rs_adaptive.hip, rs_robust.hip, rs_matte.hip: tools/unit_src.sh) whose names
 # match a pattern, compiled with exactly the flags raysnail_amd/csrc/Makefile gives that unit (its unit-flags-<unit>
 # target).
 # usage: tools/regs.sh <pattern> <unit> [extra hipcc flags ...]
