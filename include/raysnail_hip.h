@@ -718,6 +718,19 @@ int rs_probe_shade(rs_scene* s, const double* rows, uint32_t n, uint64_t seed, d
 int rs_probe_camera(rs_scene* s, const rs_camera_desc* cam, const rs_render_settings* st, const uint32_t* xys, uint32_t n,
                     int32_t centres, double* out);
 
+/* The tree rs_scene_commit staged for upload, copied out of the staged arrays themselves (what every replica
+ * receives; nothing is rebuilt), on host-only commits too. head: 8 int32 = [arity of the tree the walks use (4: the
+ * 4-wide nodes, 2: the binary nodes, 0: an empty world), its root code (a node index; ~leaf for a single object; the
+ * binary tree's root when the arity is 2), ref_order, ltop (spheres mode: the first ltop nodes are the breadth-first
+ * top the extend holds in LDS), n_nodes, n_lprim (leaf entries; 0: a leaf code ~h names prim handle h itself),
+ * n_pbox (prim handles, nested children included), stack_need]. Each of the other arrays may be null (skipped):
+ * planes: n_nodes * arity * 6 floats = per node and child slot [lo.xyz, hi.xyz] (an empty slot: +inf, -inf);
+ * child: n_nodes * arity child codes (>= 0 a node, < 0 a leaf code ~e, INT32_MIN an empty slot); lprim: n_lprim prim
+ * handles (leaf entry -> handle); pbox: n_pbox * 6 doubles = per prim handle the exact [lo.xyz, hi.xyz] the leaf
+ * test applies. Call it once with the arrays null for the sizes. Diagnostic (the tree's invariants checked on the
+ * CPU: tests/test_tree_invariants.py); additive extension of ABI 6. */
+int rs_probe_tree(const rs_scene* s, int32_t* head, float* planes, int32_t* child, int32_t* lprim, double* pbox);
+
 #ifdef __cplusplus
 }
 #endif

@@ -55,6 +55,10 @@ def load(path: str = LIB_PATH) -> C.CDLL:
     lib.orc_world_hit.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_double, C.c_double,
                                   C.c_double, C.POINTER(C.c_double)]
     lib.orc_world_hit.restype = C.c_int
+    lib.orc_bbox.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(C.c_double)]
+    lib.orc_bbox.restype = C.c_int
+    lib.orc_leaf_order.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32)]
+    lib.orc_leaf_order.restype = C.c_int
     lib.orc_tf_apply.argtypes = [C.POINTER(A.rs_transform), C.c_uint32, C.POINTER(C.c_double), C.c_double, C.c_int,
                                  C.POINTER(C.c_double)]
     lib.orc_camera_ray.argtypes = [C.POINTER(A.rs_camera_desc), C.c_double, C.c_double, C.c_uint64,
@@ -156,6 +160,20 @@ class OracleScene:
         _check(self.lib, self.lib.orc_world_hit(self.h, (C.c_double * 3)(*o), (C.c_double * 3)(*d), time, tmin, tmax,
                                                 out), "orc_")
         return list(out)
+
+    def bbox(self, handle: int) -> np.ndarray:
+        """bounding_box of the object with this handle over the scene's time range: [min.xyz, max.xyz]."""
+        out = (C.c_double * 6)()
+        _check(self.lib, self.lib.orc_bbox(self.h, C.c_uint32(handle), out), "orc_")
+        return np.array(list(out))
+
+    def leaf_order(self) -> np.ndarray:
+        """The BVH's leaves left to right, as world handles."""
+        n = C.c_uint32()
+        _check(self.lib, self.lib.orc_leaf_order(self.h, None, C.c_uint32(0), C.byref(n)), "orc_")
+        out = np.zeros(n.value, np.uint32)
+        _check(self.lib, self.lib.orc_leaf_order(self.h, out.ctypes.data_as(C.c_void_p), n, C.byref(n)), "orc_")
+        return out
 
     def shade_level(self, rows: np.ndarray, seed: int) -> np.ndarray:
         """One level of ray_color on synthetic hit records (orc_shade_level): rows (n, 18) doubles = ray o d time,

@@ -1587,6 +1587,40 @@ int orc_world_hit(orc_scene* s, const double o[3], const double d[3], double tim
     }
     return RS_OK;
 }
+// Hittable::bounding_box of handle h over the scene's time range, as orc_commit hands it to the BVH (nested children
+// have handles too): out = [min.xyz, max.xyz].
+int orc_bbox(orc_scene* s, uint32_t h, double out[6]) {
+    if ((size_t)h >= s->s.handles.size()) return fail(RS_E_INVALID, "bad handle");
+    const AABB b = s->s.handles[h]->bbox(s->s.time0, s->s.time1);
+    out[0] = b.min.x; out[1] = b.min.y; out[2] = b.min.z; out[3] = b.max.x; out[4] = b.max.y; out[5] = b.max.z;
+    return RS_OK;
+}
+// The BVH's leaves left to right (the order BVH::hit's recursion reaches them, bvh.rs:173-192), as world handles:
+// at most cap of them to out, the count to n.
+int orc_leaf_order(orc_scene* s, uint32_t* out, uint32_t cap, uint32_t* n) {
+    if (!s->s.committed) return fail(RS_E_STATE, "scene not committed");
+    const BVH& bvh = s->s.bvh;
+    uint32_t cnt = 0;
+    std::vector<int> stack;
+    if (bvh.root >= 0) stack.push_back(bvh.root);
+    while (!stack.empty()) {
+        const BVHNode& nd = bvh.nodes[stack.back()];
+        stack.pop_back();
+        if (nd.obj) {
+            uint32_t h = UINT32_MAX;
+            for (uint32_t w : s->s.world)
+                if (s->s.handles[w].get() == nd.obj) h = w;
+            if (h == UINT32_MAX) return fail(RS_E_STATE, "a leaf that is no world object");
+            if (cnt < cap) out[cnt] = h;
+            ++cnt;
+        } else {
+            stack.push_back(nd.right);
+            stack.push_back(nd.left);
+        }
+    }
+    *n = cnt;
+    return RS_OK;
+}
 // TransformStack probe (transform.rs:133-157; KAT of the reference's own test_y_rotation :187-206)
 void orc_tf_apply(const rs_transform* st, uint32_t n, const double p[3], double w, int inverse, double out[3]) {
     TransformStack ts;

@@ -258,6 +258,8 @@ def load() -> C.CDLL:
     lib.rs_probe_camera.argtypes = [VP, C.POINTER(rs_camera_desc), C.POINTER(rs_render_settings), VP, C.c_uint32,
                                     C.c_int32, VP]
     lib.rs_probe_camera.restype = C.c_int
+    lib.rs_probe_tree.argtypes = [VP, VP, VP, VP, VP, VP]
+    lib.rs_probe_tree.restype = C.c_int
     lib.rs_render.argtypes = [VP, C.POINTER(rs_camera_desc), C.POINTER(rs_render_settings), VP, VP,
                               C.POINTER(rs_render_stats)]
     lib.rs_render_device.argtypes = [VP, C.POINTER(rs_camera_desc), C.POINTER(rs_render_settings), VP, VP, VP,
@@ -317,7 +319,7 @@ EXPORTED_SYMBOLS = [
     "rs_denoise_device", "rs_denoise",
     "rs_pass_moments_device", "rs_pass_moments", "rs_pass_robust_device", "rs_pass_robust",
     "rs_denoise_var_device", "rs_denoise_var",
-    "rs_probe_world_hit", "rs_probe_samples", "rs_probe_shade", "rs_probe_camera",
+    "rs_probe_world_hit", "rs_probe_samples", "rs_probe_shade", "rs_probe_camera", "rs_probe_tree",
 ]
 
 # every symbol include/raysnail_adaptive.h declares (checked by tests/test_adaptive_abi.py)

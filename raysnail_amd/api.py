@@ -556,6 +556,23 @@ class DeviceScene:
         except Exception:
             pass
 
+    def tree(self) -> dict:
+        """The tree commit staged for upload, read back (rs_probe_tree; host-only commits too): arity, root (code),
+        ref_order, ltop, stack_need, planes (n_nodes, arity, 6) float32 = lo.xyz hi.xyz per child slot, child
+        (n_nodes, arity) int32 codes, lprim (n_lprim,) int32 (empty: a leaf code ~h names prim handle h), pbox
+        (n_pbox, 6) float64 = the exact lo.xyz hi.xyz per prim handle."""
+        head = np.zeros(8, np.int32)
+        _check(self.lib, self.lib.rs_probe_tree(self.handle, head.ctypes.data, None, None, None, None), "rs_")
+        arity, root, ref_order, ltop, n_nodes, n_lprim, n_pbox, stack_need = (int(v) for v in head)
+        planes = np.zeros((n_nodes, arity, 6), np.float32)
+        child = np.zeros((n_nodes, arity), np.int32)
+        lprim = np.zeros(n_lprim, np.int32)
+        pbox = np.zeros((n_pbox, 6), np.float64)
+        _check(self.lib, self.lib.rs_probe_tree(self.handle, head.ctypes.data, planes.ctypes.data, child.ctypes.data,
+                                                lprim.ctypes.data, pbox.ctypes.data), "rs_")
+        return {"arity": arity, "root": root, "ref_order": ref_order, "ltop": ltop, "stack_need": stack_need,
+                "planes": planes, "child": child, "lprim": lprim, "pbox": pbox}
+
     def info(self) -> A.rs_scene_info:
         """What commit built: tree arity / depth, exact stack need, scene mode (rs_scene_get_info)."""
         inf = A.rs_scene_info()

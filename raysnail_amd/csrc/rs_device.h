@@ -13,6 +13,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "rs_layout.h"
+#include "rs_cull.h"
 #include "../../include/raysnail_hip.h"
 
 #define RS_REJECTION_CAP 4096
@@ -23,7 +24,7 @@
 namespace rs {
 
 // ------------------------------------------------------------------ Vec3 ----
-struct V3 { double x, y, z; };
+// (struct V3 { double x, y, z; } is in rs_cull.h, which the CPU tests compile without this header)
 __device__ __forceinline__ V3 v3(double x, double y, double z) { return V3{x, y, z}; }
 __device__ __forceinline__ V3 operator+(V3 a, V3 b) { return v3(a.x + b.x, a.y + b.y, a.z + b.z); }
 __device__ __forceinline__ V3 operator-(V3 a, V3 b) { return v3(a.x - b.x, a.y - b.y, a.z - b.z); }

@@ -31,6 +31,7 @@
 #include "rs_host_util.h"
 #include "rs_internal.h"
 #include "rs_layout.h"
+#include "rs_cull.h"
 
 using namespace rs;
 
@@ -443,16 +444,7 @@ struct HNode {
     double hi[2][3];
     int32_t child[2];
 };
-float round_down_f(double x) {
-    if (std::isnan(x)) return (float)x;
-    float f = (float)x;
-    return ((double)f > x) ? std::nextafter(f, -INFINITY) : f;
-}
-float round_up_f(double x) {
-    if (std::isnan(x)) return (float)x;
-    float f = (float)x;
-    return ((double)f < x) ? std::nextafter(f, INFINITY) : f;
-}
+// (the planes are rounded outward with rs_cull.h's round_down_f / round_up_f, the functions the cull's CPU test uses)
 DNode to_device(const HNode& h) {
     DNode d;
     std::memset(&d, 0, sizeof(d));
@@ -3321,6 +3313,61 @@ int rs_scene_get_info(const rs_scene* s, rs_scene_info* out) {
         out->n_world = s->world.size();
         out->n_devices = (int32_t)s->reps.size();
         out->class_mask = s->class_mask;
+    });
+}
+
+int rs_probe_tree(const rs_scene* s, int32_t* head, float* planes, int32_t* child, int32_t* lprim, double* pbox) {
+    return run([&] {
+        if (!s || !head) throw Error(RS_E_INVALID, "null argument");
+        if (!s->committed) throw Error(RS_E_STATE, "scene not committed");
+        const DScene& d = s->hs.ds;
+        // the bytes staged for a pointer field of the DScene (stage()): what upload_replica copies to a device
+        auto staged = [&](const void* field) -> const std::vector<char>* {
+            const size_t fo = (size_t)((const char*)field - (const char*)&d);
+            for (const Blob& b : s->hs.blobs)
+                if (b.field_off == fo) return &b.bytes;
+            return nullptr;
+        };
+        const std::vector<char>* n2 = staged(&d.nodes);
+        const std::vector<char>* n4 = staged(&d.nodes4);
+        const std::vector<char>* lp = staged(&d.lprim);
+        const std::vector<char>* pb = staged(&d.pbox);
+        const int arity = d.root4 >= 0 ? 4 : (n2 ? 2 : 0);
+        const size_t n_nodes = arity == 4 ? (n4 ? n4->size() / sizeof(DNode4) : 0) : (n2 ? n2->size() / sizeof(DNode) : 0);
+        if (arity == 4 && !n4) throw Error(RS_E_STATE, "a 4-wide root without staged nodes");
+        head[0] = arity;
+        head[1] = arity == 4 ? d.root4 : d.root;
+        head[2] = d.ref_order;
+        head[3] = d.ltop;
+        head[4] = (int32_t)n_nodes;
+        head[5] = lp ? (int32_t)(lp->size() / sizeof(int32_t)) : 0;
+        head[6] = pb ? (int32_t)(pb->size() / sizeof(DBox64)) : 0;
+        head[7] = d.stack_need;
+        for (size_t i = 0; i < n_nodes; ++i) {
+            if (arity == 4) {
+                const DNode4& n = ((const DNode4*)n4->data())[i];
+                for (int k = 0; k < 4; ++k) {
+                    if (planes) {
+                        float* p = planes + (i * 4 + (size_t)k) * 6;
+                        p[0] = n.lo_x[k]; p[1] = n.lo_y[k]; p[2] = n.lo_z[k];
+                        p[3] = n.hi_x[k]; p[4] = n.hi_y[k]; p[5] = n.hi_z[k];
+                    }
+                    if (child) child[i * 4 + (size_t)k] = n.child[k];
+                }
+            } else {
+                const DNode& n = ((const DNode*)n2->data())[i];
+                for (int k = 0; k < 2; ++k) {
+                    if (planes)
+                        for (int q = 0; q < 3; ++q) {
+                            planes[(i * 2 + (size_t)k) * 6 + (size_t)q] = n.lo[k][q];
+                            planes[(i * 2 + (size_t)k) * 6 + 3 + (size_t)q] = n.hi[k][q];
+                        }
+                    if (child) child[i * 2 + (size_t)k] = n.child[k];
+                }
+            }
+        }
+        if (lprim && lp) std::memcpy(lprim, lp->data(), lp->size());
+        if (pbox && pb) std::memcpy(pbox, pb->data(), pb->size());
     });
 }
 

@@ -20,6 +20,7 @@
 #include "rs_device.h"
 #include "rs_internal.h"
 #include "rs_gen_perm.h"
+#include "rs_cull.h"
 
 // Translation units (Makefile): the scene-mode templates of the path kernels are compiled once per
 // mode, in parallel. RS_TU undefined: everything in one unit (tools/regs.sh, build_variant.sh);
@@ -156,114 +157,8 @@ struct TravStat {
 };
 #endif
 
-// aabb.rs:20-38 with inv = 1/d[i] precomputed per ray (the reference recomputes the same value
-// per node). Branch-free form: max/min over the three axes is equivalent to the early-exit loop
-// because t_min only grows and t_max only shrinks. This exact f64 test is applied to every
-// object's own bbox before the object is intersected.
-__device__ __forceinline__ bool slab64(const double lo[3], const double hi[3], const V3& o, const V3& inv, double tmin,
-                                       double tmax) {
-    double t0x = (lo[0] - o.x) * inv.x, t1x = (hi[0] - o.x) * inv.x;
-    double t0y = (lo[1] - o.y) * inv.y, t1y = (hi[1] - o.y) * inv.y;
-    double t0z = (lo[2] - o.z) * inv.z, t1z = (hi[2] - o.z) * inv.z;
-    if (inv.x < 0.0) { double t = t0x; t0x = t1x; t1x = t; }
-    if (inv.y < 0.0) { double t = t0y; t0y = t1y; t1y = t; }
-    if (inv.z < 0.0) { double t = t0z; t0z = t1z; t1z = t; }
-    const double a = fmax(fmax(fmax(tmin, t0x), t0y), t0z);
-    const double b = fmin(fmin(fmin(tmax, t1x), t1y), t1z);
-    return !(b <= a);
-}
-
-// Conservative f32 slab test for inner nodes: never rejects a box the exact f64 test of any
-// descendant leaf would accept. Boxes are rounded outward on the host. The ray origin is shifted
-// per axis by d = |o|*2^-20 + tiny (an expanded box [lo-d, hi+d] in effect), which absorbs the f32
-// rounding of o and of the precomputed products o'*inv (each <= |o| 2^-24); t at a plane is then one
-// FMA, t = lo*inv - (o+d)*inv. The remaining roundings (inv, fma) are relative and covered by a
-// 2^-18 slack on the interval. |inv| is clamped to 1e30 so no inf*0 / inf-inf appears.
-// An axis whose inv is infinite (a direction component that is +-0 or so small that 1 / d overflows) constrains
-// the exact test through the origin alone: (plane - o) * inf is +-inf, or a NaN that f64 min / max ignore when the
-// origin lies on the plane, so a box passes iff lo <= o <= hi. With the clamp the shift d stands in for that: the
-// far plane of a box the origin lies on gives t = d * 1e30, and d = 2^-100 (|o| = 0) made that 0.79, a range end
-// that culled every box farther than that along the ray. An axis whose inv overflows f32 gets an absolute 2^-20
-// in d instead, which puts that t beyond 9e23 whatever the origin (for a finite inv the wider box is merely
-// conservative).
-struct RayF {
-    float inv[3], opi[3], omi[3];   // inv, (o+d)*inv, (o-d)*inv
-};
-__device__ __forceinline__ float nextup_f(float f) {  // f finite, not the largest float
-    if (f == 0.0f) return 0x1p-149f;
-    const unsigned u = __float_as_uint(f);
-    return __uint_as_float(f > 0.0f ? u + 1u : u - 1u);
-}
-__device__ __forceinline__ float round_up_f(double x) {
-    const float f = (float)x;
-    return ((double)f < x) ? nextup_f(f) : f;
-}
-__device__ __forceinline__ RayF make_rayf(const V3& o, const V3& inv) {
-    RayF r;
-    const double oo[3] = {o.x, o.y, o.z}, ii[3] = {inv.x, inv.y, inv.z};
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {
-        const float of = (float)oo[k];
-        const float fi = (float)ii[k];
-        const float d = fabsf(of) * 0x1p-20f + (fabsf(fi) > 3e38f ? 0x1p-20f : 0x1p-100f);
-        // a NaN inv (a NaN direction component) stays NaN: the exact test's min / max ignore that axis (aabb.rs:20-38
-        // through f64::max / min), and so do slab32's and slab4's; clamped, it became -1e30 and culled every box whose
-        // slab on that axis does not hold the origin
-        const float iv = fi != fi ? fi : fminf(fmaxf(fi, -1e30f), 1e30f);
-        r.inv[k] = iv;
-        r.opi[k] = (of + d) * iv;
-        r.omi[k] = (of - d) * iv;
-    }
-    return r;
-}
-__device__ __forceinline__ bool slab32(const float lo[3], const float hi[3], const RayF& r, float tmin, float tmax,
-                                       float& entry) {
-    const float ax = fmaf(lo[0], r.inv[0], -r.opi[0]), bx = fmaf(hi[0], r.inv[0], -r.omi[0]);
-    const float ay = fmaf(lo[1], r.inv[1], -r.opi[1]), by = fmaf(hi[1], r.inv[1], -r.omi[1]);
-    const float az = fmaf(lo[2], r.inv[2], -r.opi[2]), bz = fmaf(hi[2], r.inv[2], -r.omi[2]);
-    float a = fmaxf(fmaxf(fmaxf(tmin, fminf(ax, bx)), fminf(ay, by)), fminf(az, bz));
-    float b = fminf(fminf(fminf(tmax, fmaxf(ax, bx)), fmaxf(ay, by)), fmaxf(az, bz));
-    a = fmaf(-fabsf(a), 0x1p-18f, a);
-    b = fmaf(fabsf(b), 0x1p-18f, b);
-    entry = a;
-    return a <= b;
-}
-
-// 4-wide nodes: the ray's direction signs pick, per axis, which of the node's lo / hi planes is
-// the entry plane -- for inv >= 0 min(ax, bx) is ax (lo with o+d), else bx (hi with o-d), exactly
-// (fma is monotone in each operand) -- so a child costs 6 FMAs and four min / max instead of the
-// pairwise min / max of slab32. The plane arrays are fetched at per-ray byte offsets in DNode4.
-struct RayF4 {
-    float inv[3], nsub[3], fsub[3];   // entry / exit plane offsets ((o+d)*inv or (o-d)*inv)
-    uint32_t noff[3];                 // byte offset of the entry-plane array (lo_* or hi_*)
-};
-__device__ __forceinline__ RayF4 make_rayf4(const RayF& r) {
-    RayF4 q;
-    constexpr uint32_t lo_off[3] = {0, 16, 32}, hi_off[3] = {48, 64, 80};
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {
-        const bool pos = r.inv[k] >= 0.0f;
-        q.inv[k] = r.inv[k];
-        q.nsub[k] = pos ? r.opi[k] : r.omi[k];
-        q.fsub[k] = pos ? r.omi[k] : r.opi[k];
-        q.noff[k] = pos ? lo_off[k] : hi_off[k];
-    }
-    return q;
-}
-// the exit-plane array is the other one of the axis: lo_off ^ hi_off = 48, 80, 112
-__device__ __forceinline__ uint32_t far_off(uint32_t noff, int k) { return noff ^ (k == 0 ? 48u : k == 1 ? 80u : 112u); }
-__device__ __forceinline__ bool slab4(float nx, float ny, float nz, float fx, float fy, float fz, const RayF4& r,
-                                      float tmin, float tmax, float& entry) {
-    const float ax = fmaf(nx, r.inv[0], -r.nsub[0]), bx = fmaf(fx, r.inv[0], -r.fsub[0]);
-    const float ay = fmaf(ny, r.inv[1], -r.nsub[1]), by = fmaf(fy, r.inv[1], -r.fsub[1]);
-    const float az = fmaf(nz, r.inv[2], -r.nsub[2]), bz = fmaf(fz, r.inv[2], -r.fsub[2]);
-    float a = fmaxf(fmaxf(fmaxf(tmin, ax), ay), az);
-    float b = fminf(fminf(fminf(tmax, bx), by), bz);
-    a = fmaf(-fabsf(a), 0x1p-18f, a);
-    b = fmaf(fabsf(b), 0x1p-18f, b);
-    entry = a;
-    return a <= b;
-}
+// The box tests -- slab64 (a leaf's own box, exact), make_rayf / slab32 and make_rayf4 / slab4 (the inner nodes' f32
+// cull) -- are in rs_cull.h, shared with the host (the planes' outward rounding) and the CPU test of the cull.
 // One 4-wide node's planes for the ray: per axis the entry (N*) and exit (F*) plane of the four child
 // boxes, fetched at the per-ray byte offsets of the ray's direction signs, and the child codes. (A 64-byte
 // node with half-float planes, rounded outward, the whole node in four loads and the arrays selected and

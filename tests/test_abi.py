@@ -70,6 +70,47 @@ def test_render_before_commit_is_state_error(hip_lib):
     lib.rs_scene_destroy(s)
 
 
+def test_probe_tree_checks_its_arguments_and_reports_the_staged_sizes(hip_lib):
+    """rs_probe_tree (the staged tree read back): a state error before the commit, RS_E_INVALID without a head, and on
+    a host-only commit of two spheres one binary-to-4-wide node with two leaves whose boxes hold the spheres."""
+    import numpy as np
+    lib = hip_lib
+    s = _scene(lib)
+    head = np.zeros(8, np.int32)
+    assert lib.rs_probe_tree(s, head.ctypes.data, None, None, None, None) == A.RS_E_STATE
+    d = A.rs_material_desc()
+    d.kind = A.RS_MAT_DIFFUSE_LIGHT
+    d.refractive = 1.0
+    mid = C.c_int32()
+    assert lib.rs_material(s, C.byref(d), C.byref(mid)) == 0
+    for x in (-2.0, 2.0):
+        h = C.c_uint32()
+        assert lib.rs_sphere(s, A.D3(x, 0, 0), 1.0, None, mid.value, C.byref(h)) == 0
+        assert lib.rs_world_add(s, h.value) == 0
+    assert lib.rs_scene_commit_devices(s, None, 0) == 0
+    assert lib.rs_probe_tree(s, None, None, None, None, None) == A.RS_E_INVALID
+    assert lib.rs_probe_tree(None, head.ctypes.data, None, None, None, None) == A.RS_E_INVALID
+    assert lib.rs_probe_tree(s, head.ctypes.data, None, None, None, None) == 0
+    arity, root, ref_order, ltop, n_nodes, n_lprim, n_pbox, stack_need = (int(v) for v in head)
+    inf = A.rs_scene_info()
+    assert lib.rs_scene_get_info(s, C.byref(inf)) == 0
+    assert (arity, root, ref_order, n_nodes, n_pbox, stack_need) == (inf.tree_arity, 0, 0, 1, 2, inf.stack_need) == (4, 0, 0, 1, 2, 0)
+    planes, child = np.full((n_nodes, arity, 6), 7.0, np.float32), np.zeros((n_nodes, arity), np.int32)
+    lprim, pbox = np.zeros(max(n_lprim, 1), np.int32), np.zeros((n_pbox, 6))
+    assert lib.rs_probe_tree(s, head.ctypes.data, planes.ctypes.data, child.ctypes.data, lprim.ctypes.data,
+                             pbox.ctypes.data) == 0
+    assert sorted(pbox.tolist()) == [[-3.0, -1.0, -1.0, -1.0, 1.0, 1.0], [1.0, -1.0, -1.0, 3.0, 1.0, 1.0]]
+    leaves = child[0][child[0] != -2 ** 31]
+    assert len(leaves) == 2 and (leaves < 0).all()
+    for k, c in enumerate(child[0]):
+        if c != -2 ** 31:
+            prim = int(lprim[~c]) if n_lprim else int(~c)
+            assert planes[0, k].tolist() == pbox[prim].tolist()
+        else:
+            assert planes[0, k].tolist() == [np.inf] * 3 + [-np.inf] * 3
+    lib.rs_scene_destroy(s)
+
+
 def test_no_lights_with_pdf_material_is_rejected_at_commit(hip_lib):
     """list.rs:49-52 would panic on % 0; the ABI returns RS_E_NO_LIGHTS before any device work."""
     lib = hip_lib

@@ -34,8 +34,9 @@ def test_million_triangle_mesh_commits():
     assert i.n_objects == 998002 and i.tree_arity == 4 and i.stack_need < 128
 
 
-def test_skewed_deep_scene_commits():
-    """Spheres whose sizes double along a line: SAH splits off one object per level near the root."""
+def skewed_world() -> World:
+    """Spheres whose sizes grow by half along a line, in a cloud of small ones (tests/test_tree_invariants.py reads the
+    tree this builds)."""
     h = HittableList()
     mat = Lambertian(C32(0.5, 0.5, 0.5))
     x = 0.0
@@ -51,7 +52,12 @@ def test_skewed_deep_scene_commits():
     lamp = Sphere((0.0, 50.0, 0.0), 1.0, DiffuseLight(C32(1.0, 1.0, 1.0)))
     lights.add(lamp)
     h.add(lamp)
-    i = _info(World(h, lights, Gradient(C32(0.3, 0.4, 0.5), C32(0.7, 0.89, 1.0))))
+    return World(h, lights, Gradient(C32(0.3, 0.4, 0.5), C32(0.7, 0.89, 1.0)))
+
+
+def test_skewed_deep_scene_commits():
+    """Spheres whose sizes double along a line: SAH splits off one object per level near the root."""
+    i = _info(skewed_world())
     assert i.tree_arity == 4 and i.stack_need >= 1
 
 
