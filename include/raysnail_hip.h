@@ -196,7 +196,10 @@ typedef struct rs_render_settings {
 #define RS_KERNEL_MATTES     5  /* k_mattes: ranked material-id mattes (rs_render_mattes) */
 typedef struct rs_render_stats {
     uint64_t samples;    /* camera samples traced */
-    uint64_t segments;   /* world.hit calls (path segments) */
+    uint64_t segments;   /* world.hit calls (path segments): the reference's count, so a frame that reports it traces
+                          * every path as the reference does. A frame rendered without statistics may trace fewer
+                          * segments (a streaming frame ends the paths whose throughput is exactly zero where the
+                          * scene allows it, csrc/rs_dead_gate.h); its pixels are the same bit for bit. */
     double   ms;         /* wall time inside the call (device work + sync) */
     double   path_ms;    /* device time of all path-tracing launches (HIP events on the call's stream) */
     uint32_t launches;   /* number of path-tracing launches in the call */

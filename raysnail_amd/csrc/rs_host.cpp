@@ -32,6 +32,7 @@
 #include "rs_internal.h"
 #include "rs_layout.h"
 #include "rs_cull.h"
+#include "rs_dead_gate.h"
 
 using namespace rs;
 
@@ -192,6 +193,7 @@ struct Slot {
     // copied into pinned host memory at its end: they size the carried-extend and shading grids of later frames of
     // the same shape (Replica::hist)
     uint32_t* h_hist = nullptr; size_t hist_cap = 0, hist_words = 0; uint64_t hist_sig = 0;
+    int hist_bank = 0;                        // Replica::hist bank of that frame (GridHist::bank)
     hipEvent_t hist_ev = nullptr; bool hist_pending = false;
     // the spheres mode's candidate records (rs_cam_cand.h), one per lattice pixel, and what they were built for: the
     // frames of one camera on this slot build them once. Written and read on the slot's own streams only.
@@ -241,8 +243,11 @@ struct Replica {
     int32_t* d_ovf = nullptr; size_t ovf_cap = 0;   // traversal-stack overflow (entries beyond the LDS part)
     DScene* d_ds = nullptr;                 // ds in device memory (what the kernels read)
     DScene uploaded{};                      // the copy last written to d_ds
-    std::vector<uint32_t> hist;             // the latest completed streaming frame's carried and queued counts (Slot::h_hist)
-    uint64_t hist_sig = 0;                  // and its schedule's signature
+    // the latest completed streaming frame's carried and queued counts (Slot::h_hist) and its schedule's signature:
+    // bank 0 of the frames that trace every path to its end, bank 1 of the frames that end zero-throughput paths
+    // (WfState::end_dead), whose late iterations carry a fraction of the former's paths
+    std::vector<uint32_t> hist[2];
+    uint64_t hist_sig[2] = {0, 0};
     std::vector<hipStream_t> pad_streams;   // dev A/B only (RS_PAD_STREAMS)
 
     // wait until no frame of this replica is in flight (before a shared buffer is replaced)
@@ -306,6 +311,8 @@ struct rs_scene {
     bool ext_split = false;                       // streaming extend in two launches per iteration in every mode (dev A/B)
     bool shade_split = true;                      // spheres mode: lean / heavy material classes in two shading launches
     bool dump_iters = false;                      // dev: per-iteration queue counts to stderr (timed frames)
+    bool dead_in_stats = false;                   // dev: statistics frames end zero-throughput paths too, so dump_iters
+                                                  // shows what the plain frames trace (their `segments` is then that count)
     uint32_t passes_stream = 0;                   // rs_render_device_passes: 0 where it pays, 1 always, 2 never (dev A/B)
     uint32_t class_mask = (1u << kWfsClasses) - 1;  // shading classes some prim has (empty queues are not launched)
     int tree_depth = 0;                     // levels of the tree in use
@@ -1314,6 +1321,20 @@ void build(rs_scene* s) {
     d.ref_order = s->ref_order ? 1 : 0;
     for (int i = 0; i < 3; ++i) { d.bg_lo[i] = s->bg_lo[i]; d.bg_hi[i] = s->bg_hi[i]; }
     d.bg_lo[3] = d.bg_hi[3] = 1.0f;
+    {   // may frames without statistics end zero-throughput paths? (rs_dead_gate.h)
+        DeadGateIn g;
+        g.spheres_mode = s->scene_mode == kSmSpheres;
+        g.moving = d.moving != 0;
+        g.mats = mats.data(); g.n_mats = (uint32_t)mats.size();
+        g.spheres = spheres.data(); g.n_spheres = (uint32_t)spheres.size();
+        std::vector<uint32_t> lsph;
+        for (int32_t h : lights)
+            if (prims[h].kind == PK_SPHERE) lsph.push_back((uint32_t)prims[h].idx);
+            else g.spheres_mode = false;
+        g.lights = lsph.data(); g.n_lights = (uint32_t)lsph.size();
+        g.bg_lo = d.bg_lo; g.bg_hi = d.bg_hi;
+        d.dead_reach = dead_gate_reach(g);
+    }
     build_limg(s);
 }
 
@@ -1869,12 +1890,15 @@ struct GridHist {
     uint64_t sig = 0;            // the frame's schedule signature
     std::vector<size_t> hoff;    // per lane: its first word
     size_t hwords = 0;           // per iteration: the paths carried in, the paths queued for shading
+    int bank = 0;                // Replica::hist bank: 1 for a frame that ends zero-throughput paths
     bool hint = false;           // Replica::hist holds a completed frame of this schedule
 };
 // the frame's history layout; takes over the counts of slots whose frames have completed (without waiting) and
 // makes room for this frame's
-GridHist hist_begin(Replica& R, Slot& L, const FrameSched& f, uint32_t n_pix, uint32_t N, uint32_t D, uint32_t n_frames) {
+GridHist hist_begin(Replica& R, Slot& L, const FrameSched& f, uint32_t n_pix, uint32_t N, uint32_t D, uint32_t n_frames,
+                    bool end_dead) {
     GridHist h;
+    h.bank = end_dead ? 1 : 0;
     h.sig = splitmix64_h(((uint64_t)n_pix << 32) ^ N) ^ splitmix64_h(((uint64_t)D << 40) ^ ((uint64_t)f.lanes << 32) ^ n_frames);
     for (const LaneSched& ln : f.lane) {
         h.sig = splitmix64_h(h.sig ^ ln.Q ^ (ln.T << 40) ^ (ln.total << 1) ^ (uint64_t)ln.finish);
@@ -1886,15 +1910,15 @@ GridHist hist_begin(Replica& R, Slot& L, const FrameSched& f, uint32_t n_pix, ui
         const hipError_t q = hipEventQuery(o.hist_ev);
         if (q == hipSuccess) {
             o.hist_pending = false;
-            R.hist.assign(o.h_hist, o.h_hist + o.hist_words);
-            R.hist_sig = o.hist_sig;
+            R.hist[o.hist_bank].assign(o.h_hist, o.h_hist + o.hist_words);
+            R.hist_sig[o.hist_bank] = o.hist_sig;
         } else {
             (void)hipGetLastError();  // hipErrorNotReady: not an error here
             if (q != hipErrorNotReady) HIP_OK(q);
         }
     }
 #ifndef RS_NO_GRID_HINT  // (dev A/B: every carried launch over a block per 256 paths of the window)
-    h.hint = R.hist_sig == h.sig && R.hist.size() == h.hwords;
+    h.hint = R.hist_sig[h.bank] == h.sig && R.hist[h.bank].size() == h.hwords;
 #endif
     if (L.hist_cap < h.hwords) {
         if (L.h_hist) { HIP_OK(hipEventSynchronize(L.hist_ev)); HIP_OK(hipHostFree(L.h_hist)); L.h_hist = nullptr; }
@@ -1908,7 +1932,7 @@ GridHist hist_begin(Replica& R, Slot& L, const FrameSched& f, uint32_t n_pix, ui
 // n_max paths capped by the earlier frame's count `word` (0 carried, 1 queued) of lane l's iteration t, + `more`
 uint64_t hist_grid(const GridHist& h, const Replica& R, uint32_t l, uint64_t t, int word, uint64_t n_max, uint64_t more = 0) {
     if (!h.hint) return n_max;
-    const uint64_t est = R.hist[h.hoff[l] + 2 * t + word];
+    const uint64_t est = R.hist[h.bank][h.hoff[l] + 2 * t + word];
     return std::min<uint64_t>(n_max, est + est / 4 + 64ull * kBlock + more);
 }
 // the frame's carried and queued counts (words 0 and 1 of each lane's iterations' counter blocks)
@@ -1921,6 +1945,7 @@ void hist_end(const GridHist& h, Slot& L, const FrameSched& f, hipStream_t S) {
     HIP_OK(hipEventRecord(L.hist_ev, S));
     L.hist_pending = true;
     L.hist_sig = h.sig;
+    L.hist_bank = h.bank;
     L.hist_words = h.hwords;
 }
 
@@ -1962,6 +1987,7 @@ struct StreamFrame {
     FrameSched f;
     GridHist h;
     bool split, split_shade;
+    bool end_dead = false;        // WfState::end_dead of the frame's launches (enqueue_streaming)
     // per lane: the samples injected by its last depth - 1 iterations (a bound on the paths it
     // carries into the next one) (the injections per iteration: P.inj)
     std::vector<uint64_t> window;
@@ -1981,6 +2007,7 @@ void StreamFrame::iteration(uint32_t l, uint64_t t) {
     const hipStream_t cs = L.lane[l];
     WfState WS = L.lane_ws[l];
     WS.tagw = tag_in_ray(c.ds, c.dc);
+    WS.end_dead = end_dead ? 1u : 0u;
     WS.counts = L.d_counts + ln.cnt_off;
     QEnt** qd = L.d_qptrs[l];
     const uint32_t n_new = ln.n_new(t);
@@ -2096,7 +2123,11 @@ void enqueue_streaming(const rs_scene* s, const rs_render_settings* st, const Fr
     for (uint32_t k = 0; k < n_frames; ++k)
         f.keys[k] = splitmix64_h(splitmix64_h(st->seed) ^ (uint64_t)(st->pass + k));
     prepare_counts(L, P.n_counts = f.n_counts, L0);
-    F.h = hist_begin(*P.R, L, f, n_pix, N, D, n_frames);
+    // Zero-throughput paths end at the scatter that zeroes them (rs_dead_gate.h) in the frames nobody counts: a frame
+    // that reports rs_render_stats::segments traces them to their ends, as the reference does. Its grids take their
+    // hints from frames of its own kind (GridHist::bank).
+    F.end_dead = (!P.counted || s->dead_in_stats) && dead_gate_camera(c.ds.host->dead_reach, c.dc.origin);
+    F.h = hist_begin(*P.R, L, f, n_pix, N, D, n_frames, F.end_dead);
     // every lane and the accumulate stream start after L0's dependencies and the counter reset
     if (!L.acc_stream) HIP_OK(hipStreamCreateWithFlags(&L.acc_stream, hipStreamNonBlocking));
     F.cand = cam_cand_records(s, c, L, L0);  // (a new camera's build: on L0, ahead of every lane)
@@ -3064,6 +3095,7 @@ int rs_scene_create(rs_scene** out) {
         v = 0; knob("RS_EXT_SPLIT", v); s->ext_split = v != 0;
         v = 0; knob("RS_SHADE_MERGED", v); if (v) s->shade_split = false;
         v = 0; knob("RS_DUMP_ITERS", v); s->dump_iters = v != 0;
+        v = 0; knob("RS_DEAD_IN_STATS", v); s->dead_in_stats = v != 0;
         v = 0; knob("RS_PASSES_STREAM", v); s->passes_stream = (uint32_t)v;
 #endif
         *out = s;

@@ -123,6 +123,9 @@ struct WfState {
     uint32_t* heads;      // bounce-synchronous sets: 2 banks x 8 shards x (count, region offset) (rs_kernels.hip Segs)
     uint32_t cap;         // records per set (the sorted path fills a set from both ends)
     uint32_t tagw;        // 1: no moving sphere -- (item, level) ride in ray_o.w instead of `tag` (rs_kernels.hip store_path)
+    uint32_t end_dead;    // 1: the streaming kernels end a path whose throughput is == 0.0 in every channel after its
+                          // scatter (it can only add +0.0: rs_dead_gate.h); set per frame by the host, 0 in every
+                          // frame that reports statistics (rs_render_stats::segments counts the dead segments too)
 };
 
 // Streaming wavefront (k_wfs_extend): the camera samples injected by one iteration. The frame's

@@ -966,6 +966,16 @@ __device__ __forceinline__ bool shade_surface(const DScene& S, const Hit& h, con
 // result is NaN and so is this one.
 __device__ __forceinline__ V3 close_path(V3 L, V3 T) { return L + T * 0.0; }
 
+// The streaming kernels' rule for WfState::end_dead frames: a path whose throughput is +-0 in every channel after a
+// scatter is not carried on. Every term it could still meet is finite in the scenes the host sets the flag for
+// (rs_dead_gate.h), so each put_rad it could reach writes 0.0 + (+-0) = +0.0 -- what close_path(0, T) writes now.
+// Only spheres-mode scenes pass the gate: the other modes' kernels compile without the test.
+template <int SM>
+__device__ __forceinline__ bool dead_path(const WfState& W, V3 T) {
+    if constexpr (SM != kSmSpheres) return false;
+    return W.end_dead && T.x == 0.0 && T.y == 0.0 && T.z == 0.0;
+}
+
 // DiffuseLight emission (light.rs:33-35) of the hit's material, as a radiance vector
 template <int R>
 __device__ __forceinline__ V3 emission(const DScene& S, const DMaterial& M0, const Hit& h) {
@@ -1778,6 +1788,7 @@ __global__ __launch_bounds__(kBlock, ext_min_waves(SM, LOBJ, PART)) void k_wfs_e
                 else if (fcls == 1) cont = shade_surface<RS_MAT_METAL, SM>(S, h, M0, M0, r, T, rng, &light_ray);
                 else cont = shade_surface<RS_MAT_DIELECTRIC, SM>(S, h, M0, M0, r, T, rng, &light_ray);
                 alive = cont && (1u < P.depth);  // the depth limit of ray_color (camera.rs:161)
+                if (dead_path<SM>(W, T)) alive = false;
                 if (!alive) {
                     const V3 L = close_path(v3(0.0, 0.0, 0.0), T);
                     put_rad(rad, item, L.x, L.y, L.z);
@@ -1835,6 +1846,7 @@ __global__ __launch_bounds__(kBlock, 2) void k_wfs_finish(const DScene* __restri
             const int bp = traverse<SM, StkT<true, stack_lds(SM)>, LOBJ>(S, r, 0.0001, bend, stk);  // world_hit
             const bool ok = finish_hit<SM>(S, bp, r, 0.0001, bend, h);
             if (!shade_step<SM>(S, ok, h, r, T, L, rng)) { open = false; break; }
+            if (dead_path<SM>(W, T)) break;  // (open: closed below with the +0.0 it would have ended with)
         }
         if (open) L = close_path(L, T);  // depth limit: the next level would return 0
         put_rad(rad, tg.x, L.x, L.y, L.z);
@@ -1899,6 +1911,7 @@ __device__ __forceinline__ void wfs_shade_batch(const DScene& S, const WfState& 
             cont = shade_surface<-1, SM>(S, h, M0, S.mats[ms], r, T, rng, &light_ray);
         }
         alive = cont && (lvl + 1 < depth);  // the depth limit of ray_color (camera.rs:161)
+        if (dead_path<SM>(W, T)) alive = false;
         if (!alive && item != ~0u) {  // absorbed or depth limit: no emission term
             const V3 L = close_path(v3(0.0, 0.0, 0.0), T);
             put_rad(rad, item, L.x, L.y, L.z);

@@ -222,6 +222,9 @@ struct DScene {
     // k_light_cand_build (null: the device had no room, or the scene gets none -- the rays walk the tree)
     LightGrid lgrid;
     const uint32_t* lcand;
+    // Host only (no kernel reads it): the scene's reach when a streaming frame rendered without statistics may end the
+    // paths whose throughput is exactly zero (rs_dead_gate.h dead_gate_reach, computed once per commit), else 0
+    double dead_reach;
 };
 
 // nodes of the spheres mode's tree top held in LDS per extend block: the root and three levels (85 nodes, 10.6 KiB;

@@ -18,6 +18,8 @@
 #   travstats per-category traversal counters (raysnail_amd/lib/trav_stats.so, a -DRS_TRAV_STATS build)
 #   abtrace  kernel traces of the bench frames, base/ then this tree (tools/trace_cmp.py)
 #   iters    per-iteration queue counts + extend / shading launches of the bench frame (dev library; tools/iter_table.py)
+#            (RS_DEAD_IN_STATS=1 in the environment: the counts of the frames rendered without statistics, which end
+#            zero-throughput paths)
 set -u
 R=${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}
 TAG=$1; shift
