@@ -478,6 +478,26 @@ public:
     // committed on first use, as by device_scene()); RS_NO_MATERIAL for a null reference (an object without a
     // material). Throws Error RS_E_INVALID for a material the scene does not hold.
     int32_t material_id(const MaterialRef& material);
+    // The handles this hittable was exported under, which trace_closest's `object` field reports for the world's own
+    // objects (committed on first use): one for most, one per triangle for a TriangleMesh, one per member for a BVH and
+    // for a TfFacade over either. Throws Error RS_E_INVALID for a hittable the scene does not hold.
+    std::vector<uint32_t> object_ids(const HittableRef& hittable);
+    // Ray queries (rs_trace_closest / rs_trace_occluded; the contract is in raysnail_hip.h): World::hit of the caller's
+    // rays, 8 doubles each = [origin.xyz, direction.xyz, time, tmax], every ray under its own range tmin..tmax.
+    // Closest hit: ids = 4 int32 per ray [hit, outside, material, object], geom = 8 doubles [t1, t2, p.xyz, n.xyz],
+    // uv = 2 doubles (geom and uv are skipped when not wanted: the vectors stay empty). Occlusion: a byte per ray.
+    struct TraceHits {
+        std::vector<int32_t> ids;
+        std::vector<double> geom, uv;
+    };
+    TraceHits trace_closest(const std::vector<double>& rays, double tmin = 1e-4, bool want_geom = true, bool want_uv = true);
+    std::vector<uint8_t> trace_occluded(const std::vector<double>& rays, double tmin = 1e-4);
+    // ... on device arrays (rs_trace_*_device: 16-byte aligned rays and geom; enqueued on `stream` of the device of
+    // entry `replica` of the committed list, not synchronised; d_geom and d_uv may be null)
+    void trace_closest(const double* d_rays, uint32_t n, double tmin, int32_t* d_ids, double* d_geom = nullptr,
+                       double* d_uv = nullptr, void* stream = nullptr, uint32_t replica = 0);
+    void trace_occluded(const double* d_rays, uint32_t n, double tmin, uint8_t* d_occluded, void* stream = nullptr,
+                        uint32_t replica = 0);
     const HittableList& hittables() const { return hittables_; }
     const HittableList& lights() const { return lights_; }
 private:
@@ -486,6 +506,7 @@ private:
     std::pair<double, double> time_range_;
     rs_scene* scene_ = nullptr;
     std::unordered_map<const void*, int32_t> materials_;  // the committed scene's: material -> handle
+    std::unordered_map<const void*, std::vector<uint32_t>> objects_;  // ... hittable -> handles (the sink's map)
 };
 
 // ------------------------------------------------------------------------------------- Camera ----

@@ -686,6 +686,59 @@ int rs_denoise_var(const float* beauty, const float* var, const float* albedo, c
                    float k_color, float sigma_normal, float sigma_depth, int32_t gamma,
                    float* out, float* out_var);
 
+/* ---- ray queries: World::hit for the caller's own rays, as the closest hit's record or as an occlusion byte ----
+ * rays: n * 8 doubles, 64 bytes per ray = [origin.xyz, direction.xyz, time, tmax]. Ray i's results go to index i of
+ * every output: nothing is reordered or compacted. Directions need not be unit vectors (t is in units of the
+ * direction's length). The medium key of every ray is 0 (rs_probe_world_hit's convention). tmin is one value per call.
+ *
+ * Each ray computes World::hit(ray, tmin..tmax) (world.rs:63-65 -> BVH::hit, bvh.rs:173-192) with its own tmax as the
+ * INITIAL end of the range: the walk starts from it and every box and object test sees it, so an object whose nearest
+ * root lies beyond tmax can still answer with another one inside the range (a sphere seen from inside, a Box, a
+ * Quadric, a CSG operand). It is not a filter on the result of a walk to +inf. Which end of the range is open is each
+ * object's own rule in the reference: spheres, rects, boxes and quadrics take tmin <= t < tmax, a triangle closes its
+ * range at tmax. No value gets a special case: a NaN tmax, a negative one and tmax < tmin do what the reference's
+ * range tests do with them (the box tests' min / max ignore a NaN end; each object's own comparisons then decide).
+ *
+ * Closest hit. d_ids (required): n * 4 int32 = [hit (0 / 1), outside (0 / 1), material id as rs_probe_world_hit
+ * reports it in field 12 (RS_NO_MATERIAL: none), object]. d_geom (may be NULL): n * 8 doubles = [t1, t2, p.xyz, n.xyz].
+ * d_uv (may be NULL): n * 2 doubles = (u, v), computed only in scenes that read them (an Image texture) and +0.0 in all
+ * others, as rs_probe_world_hit's fields 9 and 10. A miss writes ids = [0, 0, RS_TRACE_NONE, RS_TRACE_NONE], geom =
+ * [+inf, +0.0 x 7], uv = [+0.0, +0.0].
+ *   object   the handle of the world object whose record this is: the value rs_sphere .. rs_transformed returned for
+ *            the object given to rs_world_add, and first + i for triangle i of an rs_triangles call. A nested object (a
+ *            CSG operand, the child of a transform or of a medium) is never reported: its parent is. The same in every
+ *            scene mode (the numbering of rs_probe_tree's lprim and pbox).
+ *   ties     where several objects are hit at the same t1: in scenes whose tree is walked in the reference's order
+ *            (rs_scene_info / rs_probe_tree ref_order = 1) the reference's winner; otherwise one of the tied objects
+ *            (near-first walk), hit flag and t1 being the reference's in either case.
+ * Occlusion. d_occluded: n bytes, 1 iff that World::hit is Some, else 0: the closest form's hit flag, for every ray.
+ * The walk of an occlusion ray ends at its first accepted object. (Some object is accepted under its turn's range iff
+ * one is accepted under the full range -- until the first acceptance the turn's range is the full one -- so the flag
+ * does not depend on the visiting order.)
+ *
+ * Errors, all before anything touches the device. RS_E_INVALID: a NULL d_ids / d_occluded; a NULL d_rays with n > 0;
+ * d_rays or d_geom not 16-byte aligned; replica neither 0 nor below the number of committed devices. Then RS_E_STATE:
+ * before commit, or on a host-only commit (no device). n == 0 is RS_OK and launches nothing. Outputs must not overlap
+ * the rays or each other.
+ *
+ * The _device forms take device pointers on the device of entry `replica` of the committed device list (the caller
+ * picks one: a batch is not split), enqueue ONE launch on `stream` (hipStream_t, NULL = default) and return without
+ * synchronising. They allocate nothing per call, the traversal stack's overflow array aside, which is sized once per
+ * replica for the frame launches' grid (scenes whose tree fits the on-chip stack have none). The launch is a
+ * grid-stride loop of min(ceil(n / 256), 8 * the device's compute units) blocks of 256 threads, one ray per thread per
+ * trip: what a call needs beyond its arguments is bounded by the device, not by n. A ray is read with four 16-byte
+ * loads, a geom row written with four 16-byte stores and an ids row with one.
+ * rs_trace_closest / rs_trace_occluded: host arrays (no alignment asked); stage through one device allocation on
+ * replica 0, run the device form on the default stream, synchronise, copy back.
+ * No reference counterpart as an entry (the oracle's is orc_world_hit). Additive extension of ABI 6. */
+#define RS_TRACE_NONE ((int32_t)0x80000000)   /* INT32_MIN: material / object of a ray that hit nothing */
+int rs_trace_closest_device(rs_scene* s, uint32_t replica, const double* d_rays, uint32_t n, double tmin,
+                            int32_t* d_ids, double* d_geom, double* d_uv, void* stream);
+int rs_trace_occluded_device(rs_scene* s, uint32_t replica, const double* d_rays, uint32_t n, double tmin,
+                             uint8_t* d_occluded, void* stream);
+int rs_trace_closest(rs_scene* s, const double* rays, uint32_t n, double tmin, int32_t* ids, double* geom, double* uv);
+int rs_trace_occluded(rs_scene* s, const double* rays, uint32_t n, double tmin, uint8_t* occluded);
+
 /* ---- diagnostics (parity probes used by tests/) ---- */
 /* World::hit (world.rs:63-65) for n rays on the device. rays: n*7 doubles (origin, direction,
  * time); out: n*13 doubles = [hit, t1, t2, p.xyz, n.xyz, u, v, outside, material id] (u, v are

@@ -68,6 +68,8 @@ RS_MATTE_MAX_DISTINCT = 64
 RS_MATTE_ID_BACKGROUND = -2
 RS_MATTE_ID_EMPTY = -0x80000000
 RS_KERNEL_MATTES = 5
+# rs_trace_closest's: the material / object of a ray that hit nothing
+RS_TRACE_NONE = -0x80000000
 # the adaptive pass loop's (include/raysnail_adaptive.h RS_ADAPTIVE_*)
 RS_ADAPTIVE_MIN_PASSES = 2
 RS_ADAPTIVE_MAX_PASSES = 32
@@ -289,6 +291,14 @@ def load() -> C.CDLL:
     lib.rs_matte_extract_device.restype = C.c_int
     lib.rs_matte_extract.argtypes = [VP, VP, C.c_uint32, C.c_uint32, C.c_uint32, I32P, C.c_uint32, VP]
     lib.rs_matte_extract.restype = C.c_int
+    lib.rs_trace_closest_device.argtypes = [VP, C.c_uint32, VP, C.c_uint32, C.c_double, VP, VP, VP, VP]
+    lib.rs_trace_closest_device.restype = C.c_int
+    lib.rs_trace_occluded_device.argtypes = [VP, C.c_uint32, VP, C.c_uint32, C.c_double, VP, VP]
+    lib.rs_trace_occluded_device.restype = C.c_int
+    lib.rs_trace_closest.argtypes = [VP, VP, C.c_uint32, C.c_double, VP, VP, VP]
+    lib.rs_trace_closest.restype = C.c_int
+    lib.rs_trace_occluded.argtypes = [VP, VP, C.c_uint32, C.c_double, VP]
+    lib.rs_trace_occluded.restype = C.c_int
     lib.rs_probe_world_hit.argtypes = [VP, VP, C.c_uint32, C.c_double, C.c_double, VP]
     lib.rs_scene_get_info.argtypes = [VP, C.POINTER(rs_scene_info)]
     lib.rs_scene_commit_devices.argtypes = [VP, C.POINTER(C.c_int), C.c_int]
@@ -319,6 +329,7 @@ EXPORTED_SYMBOLS = [
     "rs_denoise_device", "rs_denoise",
     "rs_pass_moments_device", "rs_pass_moments", "rs_pass_robust_device", "rs_pass_robust",
     "rs_denoise_var_device", "rs_denoise_var",
+    "rs_trace_closest_device", "rs_trace_occluded_device", "rs_trace_closest", "rs_trace_occluded",
     "rs_probe_world_hit", "rs_probe_samples", "rs_probe_shade", "rs_probe_camera", "rs_probe_tree",
 ]
 

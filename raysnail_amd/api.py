@@ -380,12 +380,20 @@ def _check(lib, code: int, prefix: str):
         raise RaysnailError(code, err.decode() if isinstance(err, bytes) else str(err))
 
 
-def realize(world: World, lib, handle, prefix: str = "rs_") -> dict:
+class Realized(dict):
+    """What realize() returns: the materials' map {id(material): (material, handle)}, and as `.objects` the
+    hittables' {id(hittable): (hittable, [handles])} (the Python object is kept so that its id() stays its own)."""
+    objects: dict
+
+
+def realize(world: World, lib, handle, prefix: str = "rs_") -> Realized:
     """Replay the world description into a backend scene (libraysnail_hip or the test oracle). Returns the handle each
     material was created with: {id(material): (material, handle)} (the material is kept so that its id() stays its
-    own)."""
+    own), and as its `.objects` the handles each hittable was exported under: {id(hittable): (hittable, [handles])}
+    (a mesh, a BVH and a TfFacade over either have one per member)."""
     mat_ids = {}
-    mat_objs = {}
+    mat_objs = Realized()
+    mat_objs.objects = {}
     obj_ids = {}
     tex_ids = {}
 
@@ -456,9 +464,13 @@ def realize(world: World, lib, handle, prefix: str = "rs_") -> dict:
             return h[0]
         return h
 
-    def obj_id(o: Hittable) -> int:
-        if id(o) in obj_ids:
-            return obj_ids[id(o)]
+    def obj_id(o: Hittable):
+        if id(o) not in obj_ids:
+            h = export(o)
+            mat_objs.objects[id(o)] = (o, list(h) if isinstance(h, list) else [h])
+        return obj_ids[id(o)]
+
+    def export(o: Hittable):
         out = C.c_uint32()
         if isinstance(o, Sphere):
             call("sphere", A.D3(*o.center), o.radius, A.D3(*o.speed), mat_id(o.material), C.byref(out))
@@ -783,6 +795,51 @@ class DeviceScene:
         _check(self.lib, self.lib.rs_render_adaptive(self.handle, C.byref(cam), C.byref(st), C.byref(a), mptr,
                                                      mean.ctypes.data, var.ctypes.data, passes, C.byref(n)), "rs_")
         return mean, var, [passes[k] for k in range(n.value)]
+
+    def object_ids(self, hittable: Hittable) -> List[int]:
+        """The handles this hittable was exported under, which trace()'s `object` field reports for the world's own
+        objects: one for most, one per triangle for a TriangleMesh (in triangle order), one per member for a BVH and
+        for a TfFacade over a mesh or a BVH. Raises KeyError for a hittable the scene does not hold. (An object nested
+        in another -- a CSG operand, a TfFacade's child -- has a handle too, but a ray reports its parent.)"""
+        ent = self._materials.objects.get(id(hittable))
+        if ent is None or ent[0] is not hittable:
+            raise KeyError(f"{type(hittable).__name__} is not an object of this scene")
+        return list(ent[1])
+
+    def trace_closest_device(self, d_rays_ptr: int, n: int, tmin: float, d_ids_ptr: int, d_geom_ptr: int = 0,
+                             d_uv_ptr: int = 0, stream_ptr: int = 0, replica: int = 0) -> None:
+        """rs_trace_closest_device: World::hit of n device-resident rays ([o.xyz, d.xyz, time, tmax] doubles each,
+        16-byte aligned) on `replica`'s device, enqueued on the stream and not synchronised. ids = (n, 4) int32 [hit,
+        outside, material, object]; geom = (n, 8) float64 [t1, t2, p.xyz, n.xyz] and uv = (n, 2) float64 may be 0."""
+        _check(self.lib, self.lib.rs_trace_closest_device(self.handle, replica, d_rays_ptr or None, n, tmin,
+                                                          d_ids_ptr or None, d_geom_ptr or None, d_uv_ptr or None,
+                                                          stream_ptr or None), "rs_")
+
+    def trace_occluded_device(self, d_rays_ptr: int, n: int, tmin: float, d_occluded_ptr: int, stream_ptr: int = 0,
+                              replica: int = 0) -> None:
+        """rs_trace_occluded_device: a byte per ray, 1 iff World::hit(ray, tmin..tmax) hits anything."""
+        _check(self.lib, self.lib.rs_trace_occluded_device(self.handle, replica, d_rays_ptr or None, n, tmin,
+                                                           d_occluded_ptr or None, stream_ptr or None), "rs_")
+
+    def trace(self, rays: np.ndarray, tmin: float = 1e-4, occlusion: bool = False):
+        """Ray queries on host arrays (rs_trace_closest / rs_trace_occluded, replica 0). rays: (n, 8) float64 = [o.xyz,
+        d.xyz, time, tmax], or (n, 7) with tmax = +inf for every ray. Returns (ids (n, 4) int32, geom (n, 8) float64,
+        uv (n, 2) float64), or with occlusion=True the (n,) uint8 array."""
+        rays = np.asarray(rays, dtype=np.float64)
+        if rays.ndim != 2 or rays.shape[1] not in (7, 8):
+            raise ValueError("rays must be (n, 8) = [o.xyz, d.xyz, time, tmax] or (n, 7)")
+        if rays.shape[1] == 7:
+            rays = np.concatenate([rays, np.full((len(rays), 1), np.inf)], axis=1)
+        rays = np.ascontiguousarray(rays)
+        n = len(rays)
+        if occlusion:
+            occ = np.zeros(n, np.uint8)
+            _check(self.lib, self.lib.rs_trace_occluded(self.handle, rays.ctypes.data, n, tmin, occ.ctypes.data), "rs_")
+            return occ
+        ids, geom, uv = np.zeros((n, 4), np.int32), np.zeros((n, 8)), np.zeros((n, 2))
+        _check(self.lib, self.lib.rs_trace_closest(self.handle, rays.ctypes.data, n, tmin, ids.ctypes.data,
+                                                   geom.ctypes.data, uv.ctypes.data), "rs_")
+        return ids, geom, uv
 
 
 # ------------------------------------------------------------- frame operators' arguments ----

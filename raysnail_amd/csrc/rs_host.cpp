@@ -3564,6 +3564,93 @@ int rs_render_adaptive(rs_scene* s, const rs_camera_desc* cam, const rs_render_s
     });
 }
 
+// ---- ray queries (contract: raysnail_hip.h, rs_trace_closest_device) ----
+// The argument checks of all four entries, in the header's order: everything here comes before the device is touched.
+// `aligned`: the pointers that take 16-byte accesses on the device (the host forms stage through memory of their own).
+static Replica& trace_validate(rs_scene* s, uint32_t replica, const void* rays, uint32_t n, const void* required,
+                               std::initializer_list<const void*> aligned) {
+    if (!required) throw Error(RS_E_INVALID, "trace: null output");
+    if (!rays && n > 0) throw Error(RS_E_INVALID, "trace: null rays");
+    for (const void* p : aligned)
+        if ((uintptr_t)p & 15u) throw Error(RS_E_INVALID, "trace: rays / geom not 16-byte aligned");
+    // (replica 0 names the first committed device whatever the list holds: without one the state is what is wrong)
+    if (replica != 0 && replica >= s->reps.size()) throw Error(RS_E_INVALID, "trace: replica outside the committed devices");
+    if (!s->committed) throw Error(RS_E_STATE, "scene not committed");
+    if (s->reps.empty()) throw Error(RS_E_STATE, "scene committed without devices (host-only build)");
+    return *s->reps[replica];
+}
+// one k_trace launch on `stream` of the replica's device (occ: the occlusion form); never synchronises
+static void trace_enqueue(rs_scene* s, Replica& R, const double* d_rays, uint32_t n, double tmin, int32_t* d_ids,
+                          double* d_geom, double* d_uv, uint8_t* d_occ, hipStream_t stream) {
+    if (n == 0) return;
+    DeviceGuard g(R.device);
+    // the grid bound of the beauty frame's launches (render_enqueue: it covers trace_grid's 8 blocks per CU), so the
+    // overflow array is sized once per replica
+    const uint32_t wide = (uint32_t)std::max(1, R.n_cu * 64);
+    const uint32_t grid = std::max(std::max((uint32_t)std::max(1, R.n_cu * std::max(1, R.ext_bpc)),
+                                            (uint32_t)std::max(1, R.n_cu * std::max(1, R.shade_bpc))), wide);
+    ensure_stack_overflow(s, R, (uint64_t)grid * kBlock);
+    int sm = s->scene_mode;
+#ifdef RS_DEV_KNOBS  // dev A/B: the generic instantiation on a spheres or flat scene (tools/trace_bench.py)
+    if (std::getenv("RS_TRACE_GENERIC") && sm != kSmMarch) sm = kSmGeneric;
+#endif
+    HIP_OK(launch_trace(R.ref(), d_rays, n, tmin, d_ids, d_geom, d_uv, d_occ, sm, trace_grid(n, R.n_cu), stream));
+}
+// the host forms: one allocation on replica 0 holding the rays and every output asked for, the default stream
+static void trace_host(rs_scene* s, const double* rays, uint32_t n, double tmin, int32_t* ids, double* geom, double* uv,
+                       uint8_t* occ) {
+    Replica& R = trace_validate(s, 0, rays, n, occ ? (const void*)occ : (const void*)ids, {});
+    if (n == 0) return;
+    DeviceGuard g(R.device);
+    const size_t N = n, b_rays = N * 64, b_geom = (!occ && geom) ? N * 64 : 0, b_uv = (!occ && uv) ? N * 16 : 0,
+                 b_ids = occ ? 0 : N * 16, b_occ = occ ? N : 0;
+    const DeviceMem mem = device_alloc(b_rays + b_geom + b_uv + b_ids + b_occ);
+    char* const d = static_cast<char*>(mem.get());  // 16-byte parts first: every part starts aligned
+    double* const d_rays = reinterpret_cast<double*>(d);
+    double* const d_geom = b_geom ? reinterpret_cast<double*>(d + b_rays) : nullptr;
+    double* const d_uv = b_uv ? reinterpret_cast<double*>(d + b_rays + b_geom) : nullptr;
+    int32_t* const d_ids = b_ids ? reinterpret_cast<int32_t*>(d + b_rays + b_geom + b_uv) : nullptr;
+    uint8_t* const d_occ = b_occ ? reinterpret_cast<uint8_t*>(d + b_rays + b_geom + b_uv + b_ids) : nullptr;
+    try {
+        HIP_OK(hipMemcpy(d_rays, rays, b_rays, hipMemcpyHostToDevice));
+        trace_enqueue(s, R, d_rays, n, tmin, d_ids, d_geom, d_uv, d_occ, nullptr);
+        if (b_ids) HIP_OK(hipMemcpy(ids, d_ids, b_ids, hipMemcpyDeviceToHost));
+        if (b_geom) HIP_OK(hipMemcpy(geom, d_geom, b_geom, hipMemcpyDeviceToHost));
+        if (b_uv) HIP_OK(hipMemcpy(uv, d_uv, b_uv, hipMemcpyDeviceToHost));
+        if (b_occ) HIP_OK(hipMemcpy(occ, d_occ, b_occ, hipMemcpyDeviceToHost));
+    } catch (...) {
+        (void)hipDeviceSynchronize();  // drain what was enqueued before the buffer goes away
+        throw;
+    }
+}
+
+int rs_trace_closest_device(rs_scene* s, uint32_t replica, const double* d_rays, uint32_t n, double tmin, int32_t* d_ids,
+                            double* d_geom, double* d_uv, void* stream) {
+    return run([&] {
+        Replica& R = trace_validate(S(s), replica, d_rays, n, d_ids, {d_rays, d_geom});
+        trace_enqueue(s, R, d_rays, n, tmin, d_ids, d_geom, d_uv, nullptr, (hipStream_t)stream);
+    });
+}
+
+int rs_trace_occluded_device(rs_scene* s, uint32_t replica, const double* d_rays, uint32_t n, double tmin,
+                             uint8_t* d_occluded, void* stream) {
+    return run([&] {
+        Replica& R = trace_validate(S(s), replica, d_rays, n, d_occluded, {d_rays});
+        trace_enqueue(s, R, d_rays, n, tmin, nullptr, nullptr, nullptr, d_occluded, (hipStream_t)stream);
+    });
+}
+
+int rs_trace_closest(rs_scene* s, const double* rays, uint32_t n, double tmin, int32_t* ids, double* geom, double* uv) {
+    return run([&] { trace_host(S(s), rays, n, tmin, ids, geom, uv, nullptr); });
+}
+
+int rs_trace_occluded(rs_scene* s, const double* rays, uint32_t n, double tmin, uint8_t* occluded) {
+    return run([&] {
+        if (!occluded) throw Error(RS_E_INVALID, "trace: null output");  // (trace_host takes a null one for the closest form)
+        trace_host(S(s), rays, n, tmin, nullptr, nullptr, nullptr, occluded);
+    });
+}
+
 int rs_probe_world_hit(rs_scene* s, const double* rays, uint32_t n, double tmin, double tmax, double* out) {
     return run([&] {
         S(s);

@@ -249,6 +249,17 @@ hipError_t launch_noise(const float* px, int w, int h, float t, uint8_t* redo, u
                         unsigned long long* count, hipStream_t st);
 hipError_t launch_probe_hit(const SceneRef& s, const double* rays, uint32_t n, double tmin, double tmax, double* out, int sm,
                             hipStream_t st);
+// Ray queries (k_trace; contract in raysnail_hip.h, rs_trace_closest_device): n rays of 8 doubles, one per thread per
+// trip of a grid-stride loop over `blocks` blocks. occ non-null: the occlusion form (ids, geom, uv unused); otherwise
+// the closest-hit form (ids required; geom, uv may be null). sm picks the instantiation: the scene's own mode, or
+// kSmGeneric, which serves every mode's trees but the marcher's.
+// The grid: a block per 256 rays up to 8 per CU, so the stack-overflow array is bounded by the device, not by n.
+inline uint32_t trace_grid(uint32_t n, int n_cu) {
+    const uint64_t want = ((uint64_t)n + kBlock - 1) / kBlock, cap = 8ull * (uint64_t)(n_cu > 0 ? n_cu : 1);
+    return (uint32_t)(want < cap ? want : cap);
+}
+hipError_t launch_trace(const SceneRef& s, const double* rays, uint32_t n, double tmin, int32_t* ids, double* geom,
+                        double* uv, uint8_t* occ, int sm, uint32_t blocks, hipStream_t st);
 // First-hit feature buffers (k_features): the lattice pixels of p (n_pix_local, width, height, row_begin, row_step,
 // sqrt_spp, key_base, mask) into the full frames out_albedo = [r, g, b, coverage] and out_normal = [nx, ny, nz, depth]
 // (RGBA f32; either may be null). seg_counter (may be null): += the world.hit calls. At most max_blocks blocks.

@@ -27,7 +27,8 @@
 // RS_TU = -1: the common unit (mode-independent kernels, the launchers that dispatch on the scene
 // mode); RS_TU = k >= 0: scene mode k's launch_*_sm<k> instantiations only; RS_TU = 6: the feature
 // unit (k_features and k_features_spec with the generic World::hit; no scene mode's launchers);
-// RS_TU = 7: the matte unit (k_mattes with the generic World::hit, likewise).
+// RS_TU = 7: the matte unit (k_mattes with the generic World::hit, likewise); RS_TU = 8: the ray-query unit
+// (k_trace with the generic, the spheres and the flat World::hit; the RayMarcher variant is in unit 5).
 // RS_TU_SUFFIX names the unit in its exported debug symbol (nothing, _c, _<k>).
 #define RS_PASTE_(a, b) a##b
 #define RS_PASTE(a, b) RS_PASTE_(a, b)
@@ -47,6 +48,10 @@
 #define RS_TU_COMMON 0
 #define RS_TU_MODES 0
 #define RS_TU_SUFFIX _7
+#elif RS_TU == 8
+#define RS_TU_COMMON 0
+#define RS_TU_MODES 0
+#define RS_TU_SUFFIX _8
 #else
 #define RS_TU_COMMON 0
 #define RS_TU_MODES 1
@@ -2824,6 +2829,159 @@ hipError_t launch_mattes(const SceneRef& s, const DCamera& c, const PathParams& 
 #endif
 #endif  // the matte unit or the marcher unit
 
+#if !defined(RS_TU) || RS_TU == 5 || RS_TU == 8
+// Ray queries (the contract is rs_trace_closest_device's in raysnail_hip.h): World::hit of the caller's
+// own rays, each under its own range [tmin, tmax), as the closest hit's record or as the occlusion byte. SM: kSmGeneric
+// (it serves the nest modes' trees too), kSmSpheres and kSmFlat in the ray-query unit, kSmMarch in the marcher's.
+
+// traverse() from an initial range end tmax instead of +inf -- a sibling, not a defaulted argument: traverse() is
+// inlined into every path kernel, and they are to stay the binaries they were. The walks are traverse()'s in-place ones
+// (no deferred leaf lists, no LDS tree top), through the same node steps and the same leaf test. ANY: the walk ends at
+// the first accepted leaf. Some leaf is accepted under its turn's range iff one is accepted under the full range (a
+// turn's range is the full one until the first acceptance), so the flag is World::hit's for any visiting order.
+template <int SM, bool ANY, class STK>
+__device__ __forceinline__ int traverse_range(const DScene& S, const Ray& r, double tmin, double tmax, double& bend_out,
+                                              const STK& stk) {
+    if (S.root < 0) return -1;
+    const RayC rc = ray_consts(r);
+    const RayF rf = make_rayf(r.o, rc.inv);
+    const float tmin32 = -round_up_f(-tmin);
+    double best = tmax, bend = tmax;
+    float best32 = round_up_f(tmax);  // (a NaN end stays NaN: slab32's and slab64's min ignore it, as aabb.rs's does)
+    int bp = -1;
+    TravStat st;
+    if ((SM == kSmNest0 || SM == kSmNest2 || generic_mode(SM)) && S.root4 >= 0 && S.ref_order) {
+        walk4_inorder<false, false>(S, rf, tmin32, best32, stk, st, [&](int c) RS_INLINE_LAMBDA {
+            st.leaf();
+            leaf_tighten<SM>(S, c, r, rc, tmin, best, bend, bp, best32);
+            // the shared loop has no exit: with the end at -inf the slack makes the exit side NaN, every later box
+            // test fails and the stack drains without another leaf test
+            if (ANY && bp >= 0) best32 = -__builtin_huge_valf();
+        });
+    } else if (S.root4 >= 0 && !S.ref_order) {
+        const RayF4 rq = make_rayf4(rf);
+        int node = S.root4, sp = 0;
+        while (node >= 0 && !(ANY && bp >= 0)) {
+            st.node();
+            node = bvh4_step<SM>(S, r, rc, rq, tmin, tmin32, node, sp, stk, best, bend, bp, best32, st);
+        }
+    } else {
+        int k = 0, node = S.root, sp = 0;
+        while (true) {
+            const DNode& N = S.nodes[node];
+            const int c = N.child[k];
+            float e;
+            if (c != INT32_MIN && slab32(N.lo[k], N.hi[k], rf, tmin32, best32, e)) {
+                if (c < 0) {
+                    st.leaf();
+                    leaf_tighten<SM>(S, c, r, rc, tmin, best, bend, bp, best32);
+                    if (ANY && bp >= 0) break;
+                } else {
+                    if (k == 0) { stk.put(sp, node); ++sp; }  // come back for the right child
+                    node = c;
+                    k = 0;
+                    continue;
+                }
+            }
+            if (k == 0) { k = 1; continue; }
+            if (sp == 0) break;
+            --sp;
+            node = stk.get(sp);
+            k = 1;
+        }
+    }
+    st.store();
+    bend_out = bend;
+    return (bp >= 0 && S.lprim) ? S.lprim[bp] : bp;
+}
+
+// waves per SIMD the instantiations are compiled for: the generic World::hit's two (k_probe_hit's, k_features'), the
+// marcher's one, and four for the spheres and flat leaf tests (tools/regs.sh: no scratch; profiles/trace/regs.txt)
+constexpr int trace_min_waves(int sm) { return sm == kSmMarch ? 1 : sm == kSmGeneric ? 2 : 4; }
+typedef int i4u __attribute__((ext_vector_type(4), aligned(4)));  // ids rows: int32-aligned, one 16-byte store
+
+// One ray per thread per trip of a grid-stride loop (the host's grid is bounded by the device, not by n: so is the
+// stack-overflow array). No LDS is shared between threads and no barrier stands in the loop, whose trip count is the
+// thread's own. A ray is four 16-byte loads, a geom row four 16-byte stores, an ids row one.
+// ANY = false: ids (required), geom and uv (either may be null); ANY = true: occ alone.
+template <int SM, bool ANY>
+__global__ __launch_bounds__(kBlock, trace_min_waves(SM)) void k_trace(
+    const DScene* __restrict__ Sp, const double* __restrict__ rays, uint32_t n, double tmin, int32_t* __restrict__ ids,
+    double* __restrict__ geom, double* __restrict__ uv, uint8_t* __restrict__ occ) {
+    const DScene& S = *Sp;  // the scene lives in device memory: no by-value copy in scratch
+    __shared__ int stk_all[stack_lds(SM) * kBlock];
+    const StkT<true, stack_lds(SM)> stk = make_stk<true, stack_lds(SM)>(S, stk_all);
+    const uint64_t stride = (uint64_t)gridDim.x * kBlock;
+    for (uint64_t i = (uint64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += stride) {
+        const RS_GLOBAL d2v* const rp = (const RS_GLOBAL d2v*)rays + 4 * i;
+        const d2v a = rp[0], b = rp[1], c = rp[2], d = rp[3];
+        Ray r;
+        r.o = v3(a.x, a.y, b.x); r.d = v3(b.y, c.x, c.y); r.time = d.x;
+        r.key = 0;  // medium key 0 (rs_probe_world_hit's convention, orc_world_hit's)
+        const double tmax = d.y;
+        double bend;
+        const int bp = traverse_range<SM, ANY>(S, r, tmin, tmax, bend, stk);
+        if constexpr (ANY) {
+            occ[i] = bp >= 0 ? 1 : 0;
+        } else {
+            Hit h;
+            h.u = 0.0; h.v = 0.0;
+            const bool hit = finish_hit<SM>(S, bp, r, tmin, bend, h);  // under the range the winner was accepted under
+            i4u row;
+            row.x = hit ? 1 : 0; row.y = hit && h.outside ? 1 : 0;
+            row.z = hit ? h.mat : INT32_MIN; row.w = hit ? bp : INT32_MIN;  // (RS_TRACE_NONE)
+            *((RS_GLOBAL i4u*)ids + i) = row;
+            if (geom) {
+                RS_GLOBAL d2v* const g = (RS_GLOBAL d2v*)geom + 4 * i;
+                d2v g0, g1, g2, g3;
+                g0.x = hit ? h.t1 : RS_INF; g0.y = hit ? h.t2 : 0.0;
+                g1.x = hit ? h.p.x : 0.0; g1.y = hit ? h.p.y : 0.0;
+                g2.x = hit ? h.p.z : 0.0; g2.y = hit ? h.n.x : 0.0;
+                g3.x = hit ? h.n.y : 0.0; g3.y = hit ? h.n.z : 0.0;
+                g[0] = g0; g[1] = g1; g[2] = g2; g[3] = g3;
+            }
+            if (uv) {  // (u, v) exist only in scenes that read them
+                const bool has = hit && S.uv;
+                uv[2 * i] = has ? h.u : 0.0;
+                uv[2 * i + 1] = has ? h.v : 0.0;
+            }
+        }
+    }
+}
+
+// blocks: the grid the caller sized the stack overflow for (rs_internal.h trace_grid)
+template <int SM>
+static hipError_t trace_launch(const SceneRef& s, const double* rays, uint32_t n, double tmin, int32_t* ids, double* geom,
+                               double* uv, uint8_t* occ, uint32_t blocks, hipStream_t st) {
+    if (!blocks) return hipSuccess;
+    if (occ)
+        hipLaunchKernelGGL((k_trace<SM, true>), dim3(blocks), dim3(kBlock), 0, st, s.dev, rays, n, tmin, ids, geom, uv, occ);
+    else
+        hipLaunchKernelGGL((k_trace<SM, false>), dim3(blocks), dim3(kBlock), 0, st, s.dev, rays, n, tmin, ids, geom, uv, occ);
+    return hipGetLastError();
+}
+#if !defined(RS_TU) || RS_TU == 5
+hipError_t trace_march(const SceneRef& s, const double* rays, uint32_t n, double tmin, int32_t* ids, double* geom,
+                       double* uv, uint8_t* occ, uint32_t blocks, hipStream_t st) {
+    return trace_launch<kSmMarch>(s, rays, n, tmin, ids, geom, uv, occ, blocks, st);
+}
+#endif
+#if !defined(RS_TU) || RS_TU == 8
+hipError_t trace_generic(const SceneRef& s, const double* rays, uint32_t n, double tmin, int32_t* ids, double* geom,
+                         double* uv, uint8_t* occ, uint32_t blocks, hipStream_t st) {
+    return trace_launch<kSmGeneric>(s, rays, n, tmin, ids, geom, uv, occ, blocks, st);
+}
+hipError_t trace_spheres(const SceneRef& s, const double* rays, uint32_t n, double tmin, int32_t* ids, double* geom,
+                         double* uv, uint8_t* occ, uint32_t blocks, hipStream_t st) {
+    return trace_launch<kSmSpheres>(s, rays, n, tmin, ids, geom, uv, occ, blocks, st);
+}
+hipError_t trace_flat(const SceneRef& s, const double* rays, uint32_t n, double tmin, int32_t* ids, double* geom,
+                      double* uv, uint8_t* occ, uint32_t blocks, hipStream_t st) {
+    return trace_launch<kSmFlat>(s, rays, n, tmin, ids, geom, uv, occ, blocks, st);
+}
+#endif
+#endif  // the ray-query unit or the marcher unit
+
 #if !defined(RS_TU) || RS_TU == 1
 // The candidates of a beam: the 4-wide tree walked with the beam against each child box's bounding sphere, the sphere
 // of every leaf reached tested with the same criterion (k_cam_cand_build's comment; more than kCandMax candidates, a
@@ -3210,6 +3368,24 @@ hipError_t launch_probe_hit(const SceneRef& s, const double* rays, uint32_t n, d
     if (sm == kSmMarch) return probe_hit_march(s, rays, n, tmin, tmax, out, blocks, st);
     hipLaunchKernelGGL(k_probe_hit<kSmGeneric>, dim3(blocks), dim3(kBlock), 0, st, s.dev, rays, n, tmin, tmax, out);
     return hipGetLastError();
+}
+
+// the ray queries' instantiations live in the ray-query unit and, the marcher's, in its own
+#define RS_TRACE_ARGS const SceneRef& s, const double* rays, uint32_t n, double tmin, int32_t* ids, double* geom, \
+                      double* uv, uint8_t* occ, uint32_t blocks, hipStream_t st
+hipError_t trace_march(RS_TRACE_ARGS);
+hipError_t trace_generic(RS_TRACE_ARGS);
+hipError_t trace_spheres(RS_TRACE_ARGS);
+hipError_t trace_flat(RS_TRACE_ARGS);
+#undef RS_TRACE_ARGS
+hipError_t launch_trace(const SceneRef& s, const double* rays, uint32_t n, double tmin, int32_t* ids, double* geom,
+                        double* uv, uint8_t* occ, int sm, uint32_t blocks, hipStream_t st) {
+    switch (sm) {
+    case kSmMarch: return trace_march(s, rays, n, tmin, ids, geom, uv, occ, blocks, st);
+    case kSmSpheres: return trace_spheres(s, rays, n, tmin, ids, geom, uv, occ, blocks, st);
+    case kSmFlat: return trace_flat(s, rays, n, tmin, ids, geom, uv, occ, blocks, st);
+    default: return trace_generic(s, rays, n, tmin, ids, geom, uv, occ, blocks, st);  // the nest modes' trees too
+    }
 }
 
 hipError_t launch_accumulate(const double* rad, double* acc, uint32_t n_pix, uint32_t n_samp_batch,

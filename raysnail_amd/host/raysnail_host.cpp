@@ -280,7 +280,8 @@ World::~World() {
 
 World::World(World&& o) noexcept
     : hittables_(std::move(o.hittables_)), lights_(std::move(o.lights_)), background_(o.background_),
-      time_range_(o.time_range_), scene_(o.scene_), materials_(std::move(o.materials_)) {
+      time_range_(o.time_range_), scene_(o.scene_), materials_(std::move(o.materials_)),
+      objects_(std::move(o.objects_)) {
     o.scene_ = nullptr;
 }
 
@@ -293,6 +294,7 @@ World& World::operator=(World&& o) noexcept {
         time_range_ = o.time_range_;
         scene_ = o.scene_;
         materials_ = std::move(o.materials_);
+        objects_ = std::move(o.objects_);
         o.scene_ = nullptr;
     }
     return *this;
@@ -311,7 +313,8 @@ void World::export_to(SceneSink& sink) const {
 
 // export the world into a new scene and commit it: to the current device, or to `devices` when given
 static rs_scene* commit_world(const World& w, const std::vector<int>* devices,
-                              std::unordered_map<const void*, int32_t>& materials) {
+                              std::unordered_map<const void*, int32_t>& materials,
+                              std::unordered_map<const void*, std::vector<uint32_t>>& objects) {
     rs_scene* s = nullptr;
     check_rs(rs_scene_create(&s));
     try {
@@ -319,6 +322,7 @@ static rs_scene* commit_world(const World& w, const std::vector<int>* devices,
         w.export_to(sink);
         check_rs(devices ? rs_scene_commit_devices(s, devices->data(), (int)devices->size()) : rs_scene_commit(s));
         materials = std::move(sink.materials);
+        objects = std::move(sink.objects);
     } catch (...) {
         rs_scene_destroy(s);
         throw;
@@ -327,13 +331,13 @@ static rs_scene* commit_world(const World& w, const std::vector<int>* devices,
 }
 
 rs_scene* World::device_scene() {
-    if (!scene_) scene_ = commit_world(*this, nullptr, materials_);
+    if (!scene_) scene_ = commit_world(*this, nullptr, materials_, objects_);
     return scene_;
 }
 
 rs_scene* World::device_scene(const std::vector<int>& devices) {
     if (scene_) throw Error(RS_E_STATE, "world already committed");
-    scene_ = commit_world(*this, &devices, materials_);
+    scene_ = commit_world(*this, &devices, materials_, objects_);
     return scene_;
 }
 
@@ -343,6 +347,50 @@ int32_t World::material_id(const MaterialRef& material) {
     const auto it = materials_.find(material.get());
     if (it == materials_.end()) throw Error(RS_E_INVALID, "material_id: not a material of this world");
     return it->second;
+}
+
+std::vector<uint32_t> World::object_ids(const HittableRef& hittable) {
+    if (!hittable) throw Error(RS_E_INVALID, "object_ids: null hittable");
+    device_scene();
+    const auto it = objects_.find(hittable.get());
+    if (it == objects_.end()) throw Error(RS_E_INVALID, "object_ids: not an object of this world");
+    return it->second;
+}
+
+static uint32_t trace_count(const std::vector<double>& rays) {
+    if (rays.size() % 8 != 0) throw Error(RS_E_INVALID, "trace: rays must hold 8 doubles each");
+    if (rays.size() / 8 > 0xFFFFFFFFull) throw Error(RS_E_INVALID, "trace: too many rays for one call");
+    return (uint32_t)(rays.size() / 8);
+}
+
+World::TraceHits World::trace_closest(const std::vector<double>& rays, double tmin, bool want_geom, bool want_uv) {
+    const uint32_t n = trace_count(rays);
+    TraceHits out;
+    out.ids.resize((size_t)n * 4);
+    if (want_geom) out.geom.resize((size_t)n * 8);
+    if (want_uv) out.uv.resize((size_t)n * 2);
+    int32_t none[4];  // (an empty vector has no address to give: the library still checks the scene's state)
+    check_rs(rs_trace_closest(device_scene(), rays.data(), n, tmin, n ? out.ids.data() : none,
+                              want_geom && n ? out.geom.data() : nullptr, want_uv && n ? out.uv.data() : nullptr));
+    return out;
+}
+
+std::vector<uint8_t> World::trace_occluded(const std::vector<double>& rays, double tmin) {
+    const uint32_t n = trace_count(rays);
+    std::vector<uint8_t> out(n);
+    uint8_t none;
+    check_rs(rs_trace_occluded(device_scene(), rays.data(), n, tmin, n ? out.data() : &none));
+    return out;
+}
+
+void World::trace_closest(const double* d_rays, uint32_t n, double tmin, int32_t* d_ids, double* d_geom, double* d_uv,
+                          void* stream, uint32_t replica) {
+    check_rs(rs_trace_closest_device(device_scene(), replica, d_rays, n, tmin, d_ids, d_geom, d_uv, stream));
+}
+
+void World::trace_occluded(const double* d_rays, uint32_t n, double tmin, uint8_t* d_occluded, void* stream,
+                           uint32_t replica) {
+    check_rs(rs_trace_occluded_device(device_scene(), replica, d_rays, n, tmin, d_occluded, stream));
 }
 
 // ------------------------------------------------------------------------------------- Camera ----
