@@ -9,6 +9,7 @@
 // The per-primitive / per-material functions cite their reference lines below.
 #pragma once
 #include "../../include/rs_crmath.h"
+#include "rs_crfast.h"
 #include "rs_raymarch.h"
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -936,7 +937,7 @@ __device__ __forceinline__ V3 random_cosine_direction(Rng& rng) {
     double q2 = sqrt(r2);
     double phi = 2.0 * RS_PI * r1;
     double sp, cp;
-    rs_cr::sincos_cr(phi, &sp, &cp);  // correctly rounded (rs_crmath.h)
+    rs_crfast::sincos(phi, &sp, &cp);  // correctly rounded (rs_crmath.h's bits, rs_crfast.h)
     return v3(cp * q2, sp * q2, sqrt(1.0 - r2));
 }
 // vec3.rs:115-126
@@ -946,7 +947,7 @@ __device__ __forceinline__ V3 random_cosine_direction_exponent(double e, Rng& rn
     double st = sqrt(1.0 - r2 * r2);
     double phi = 2.0 * RS_PI * r1;
     double sp, cp;
-    rs_cr::sincos_cr(phi, &sp, &cp);
+    rs_crfast::sincos(phi, &sp, &cp);
     return v3(cp * st, sp * st, r2);
 }
 
@@ -956,7 +957,7 @@ __device__ __forceinline__ V3 random_unit(Rng& rng) {
     const double z = rng.range(-1.0, 1.0);
     const double r = sqrt(1.0 - z * z);
     double sa, ca;
-    rs_cr::sincos_cr(a, &sa, &ca);
+    rs_crfast::sincos(a, &sa, &ca);
     return v3(r * ca, r * sa, z);
 }
 
@@ -1115,7 +1116,7 @@ __device__ __forceinline__ void tex_color(const DScene& S, const DMaterial& m, V
     }
     bool odd = false;
     if (m.tex_kind == RS_TEX_CHECKER) {
-        odd = rs_cr::sin3_negative(m.tex_scale * p.x, m.tex_scale * p.y, m.tex_scale * p.z);
+        odd = rs_crfast::sin3_negative(m.tex_scale * p.x, m.tex_scale * p.y, m.tex_scale * p.z);
     }
     const float* s = odd ? m.odd : m.even;
     c[0] = s[0]; c[1] = s[1]; c[2] = s[2];

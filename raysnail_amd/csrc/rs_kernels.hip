@@ -934,7 +934,8 @@ __device__ __forceinline__ bool shade_surface(const DScene& S, const Hit& h, con
         return false;  // DiffuseLight reached through MixedMaterial: scatter None, no emission
     }
     // non-skip_pdf branch (camera.rs:194-247)
-    double light_multi = 1.0, pdf_val;
+    double light_multi = 1.0, pdf_val = 0.0;
+    bool unit_mult = false;  // the BSDF branch's pdf_value(sd) / pdf_value(sd) without its two divisions (RS_CRFAST)
     Ray nr;
     nr.time = ray.time;
     if (rng.gen() < 0.5) {
@@ -952,12 +953,22 @@ __device__ __forceinline__ bool shade_surface(const DScene& S, const Hit& h, con
     } else {
         V3 sd = (KIND == RS_MAT_LAMBERTIAN) ? onb_local(pdf.n, random_cosine_direction(rng))
                                             : pdf_generate<rich_of(SM)>(pdf, rng);
-        pdf_val = pdf_value<rich_of(SM)>(pdf, sd);
+        // pdf_val and mult's numerator are the same function of the same direction here. For the cosine and the
+        // reflection pdf that is max(c / pi, 0) of one dot product c: with 2^-1000 <= c < inf the quotient c / pi
+        // is positive, finite and normal, so mult is x / x = 1.0 exactly. Every other c takes the expression below.
+        if (RS_CRFAST && (pdf.kind == kPdfCosine || pdf.kind == kPdfReflection)) {
+            const double cs = dot(sd, pdf.kind == kPdfCosine ? pdf.n.w : pdf.refl.w);
+            unit_mult = cs >= 0x1p-1000 && cs < INFINITY;
+        }
+        if (!unit_mult) pdf_val = pdf_value<rich_of(SM)>(pdf, sd);
         nr.o = h.p;
         nr.d = sd;
     }
-    if (pdf_val <= 0.0 || pdf_val != pdf_val) pdf_val = 1e-5;
-    const double mult = pdf_value<rich_of(SM)>(pdf, nr.d) / pdf_val;
+    double mult = 1.0;
+    if (!unit_mult) {
+        if (pdf_val <= 0.0 || pdf_val != pdf_val) pdf_val = 1e-5;
+        mult = pdf_value<rich_of(SM)>(pdf, nr.d) / pdf_val;
+    }
     T = v3(((double)c[0] * (light_multi * T.x)) * mult, ((double)c[1] * (light_multi * T.y)) * mult,
            ((double)c[2] * (light_multi * T.z)) * mult);
     ray = nr;

@@ -8,7 +8,7 @@ R=$(cd "$(dirname "$0")/.." && pwd)
 N=$1; shift
 B=/tmp/rs_var_$N; mkdir -p $B
 M="make -s --no-print-directory -C $R/raysnail_amd/csrc"
-for t in common 0 1 2 3 4 5 6 7; do
+for t in common 0 1 2 3 4 5 6 7 8; do
   if [ -n "${NOUNIT:-}" ] && [ $t != common ]; then F="$($M unit-flags-common | sed 's/-DRS_TU=-1//') -DRS_TU=$t"; else F=$($M unit-flags-$t); fi
   /opt/rocm/bin/hipcc $F "$@" -c $R/raysnail_amd/csrc/rs_kernels.hip -o $B/k$t.o &
 done
